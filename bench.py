@@ -2,6 +2,7 @@
 """Headline benchmark: voxels/s of the voxelwise VB hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c1|c4|c5] [--voxels V | --grid N]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one complete pass of the hot path (every voxel of this rank's shard fitted to VB
 convergence: fabber_vb_run_device = Vb::DoCalculationsVoxelwise) over one batch of synthetic
@@ -11,7 +12,10 @@ white noise, 100 timepoints, max-iterations 50, 1e6 voxels PER GPU (weak scaling
 N x 1e6 voxels; voxels are independent, so the shard is a contiguous block and the only
 collective is one tiny all-reduce of [sum F or noise checksum, sum iterations, bad voxels]).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement). A plain run sets up, warms up, times the K steps,
+writes the outputs of the last step if --dump-outputs is given, and prints that line. With --full the line also
+carries the objects below, each measured outside the timed steps (roofline and the per-step HIP events behind it,
+the CPU baseline, the e2e child):
   roofline     - HBM roofline of the VB kernel: algorithmic bytes (4 T in + 4 rows out per voxel,
                  SURVEY.md section 8d) / HIP-event kernel time, against 8 TB/s; `traffic` = HBM bytes
                  per launch from the PMC passes committed under profiles/ (tools/pmc_passes.sh). The
@@ -23,6 +27,12 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with two extra o
   e2e          - (N = 1) the boundary itself with PCIe and host work included - fabber_vb_run_host through host pointers and
                  the reference's C ABI stage by stage - measured in a CHILD process without PyTorch (--e2e-child): the
                  system's HIP runtime, as a caller of the C ABI has it. Never the headline `value`.
+
+--dump-outputs DIR writes what the last timed step computed - the per-voxel arrays a caller of the timed path receives
+(mvn, status, setup_failed, iterations; free_energy with --need-f) - as DIR/<name>.npy in float64. Above 64 MB in all,
+the same seeded sample of voxels (sorted, numpy default_rng(0)) is taken from every array. The inputs are seeded, so
+two builds run with the same arguments can be compared output for output. With --gpus N > 1, rank 0's shard;
+--workload c5 --gpus N > 1 (the multi-slab run) hands its caller no mvn, so its dump has none either.
 """
 import argparse
 import json
@@ -83,6 +93,25 @@ def make_problem(w, V, seed, need_f):
     if kind == "poly":
         return cases.poly_problem(V, w["T"], w["degree"], seed=seed, max_iterations=w["its"], need_f=need_f)
     return cases.linear_problem(V, w["T"], seed=seed, max_iterations=w["its"], need_f=need_f, noise=vbabi.NOISE_AR1)
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, res, need_f):
+    """--dump-outputs: the per-voxel arrays of `res` (a results dict of the engine) as float64 .npy files, a seeded
+    sample of voxels when all of them would exceed DUMP_BYTES. free_energy only with need_f (otherwise never filled)."""
+    if not out_dir:
+        return
+    n = len(res["status"])
+    arrays = {k: np.asarray(v) for k, v in res.items()
+              if isinstance(v, np.ndarray) and v.shape[-1:] == (n,) and (need_f or k != "free_energy")}
+    per_voxel = sum(a.size // n for a in arrays.values()) * 8
+    keep = min(n, (DUMP_BYTES - 4096 * len(arrays)) // per_voxel)
+    idx = None if keep == n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a if idx is None else a[..., idx], dtype=np.float64))
+
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 FP64_VALU_PEAK_TFLOPS = 78.6   # 256 CU x 4 SIMD x 16 lanes/clk x 2 flop x 2.4 GHz (= half the 157.3 TF fp32 vector peak)
@@ -149,16 +178,29 @@ def bench_spatial(args, world, rank, device):
     for _ in range(args.warmup):
         prob.run_spatial(sp)
     torch.cuda.synchronize(device)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if args.full else []
     t0 = time.perf_counter()
     for i in range(args.steps):
-        ev[i][0].record()
+        if ev:
+            ev[i][0].record()
         prob.run_spatial(sp)  # returns when the stream has drained
-        ev[i][1].record()
+        if ev:
+            ev[i][1].record()
     torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - t0
-    dev_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     got = prob.results()
+    dump_outputs(args.dump_outputs, got, bool(args.need_f))
+    result = {"metric": "voxels/sec to VB convergence", "value": V * args.steps / elapsed, "unit": "voxels/s", "n_gpus": 1,
+              "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+              "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+              "config": {"workload": w["desc"].replace("(type M)", "(type %s)" % args.prior_type), "grid": [n, n, n], "total_voxels": V, "timepoints": T, "params": P,
+                         "iterations": w["its"], "need_f": bool(args.need_f), "input_dtype": "f32", "spatial_prior_type": args.prior_type,
+                         "bad_voxels": int(np.count_nonzero(got["status"]))},
+              "roofline": None, "cpu_baseline": None}
+    if not args.full:
+        print(json.dumps(result), flush=True)
+        return result
+    dev_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     rows = holder.n_mvn_rows
     alg_bytes = (4 * T + 4 * rows + w["its"] * 6 * 8) * V  # C3's bytes + 6 neighbour means per iteration
     roofline = {"bound": "hbm", "kernel": "spatial<exp,%d>: vb_spatial_* kernels of one run" % P,
@@ -201,13 +243,8 @@ def bench_spatial(args, world, rank, device):
                          "oracle/liboracle.so single thread, %.1f s" % (m, cpu_s),
                "gpu_over_cpu_single_thread": (V / (dev_ms * 1e-3)) / (len(keep) / cpu_s),
                "gpu_vs_cpu_on_the_block": tolist(stats), "cpu_vs_cpu_fma_build_floor": tolist(floor)}
-    result = {"metric": "voxels/sec to VB convergence", "value": V * args.steps / elapsed, "unit": "voxels/s", "n_gpus": 1,
-              "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-              "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-              "config": {"workload": w["desc"].replace("(type M)", "(type %s)" % args.prior_type), "grid": [n, n, n], "total_voxels": V, "timepoints": T, "params": P,
-                         "iterations": w["its"], "need_f": bool(args.need_f), "input_dtype": "f32", "spatial_prior_type": args.prior_type,
-                         "bad_voxels": int(np.count_nonzero(got["status"])), "ms_per_iteration": dev_ms / w["its"]},
-              "roofline": roofline, "cpu_baseline": cpu}
+    result["config"]["ms_per_iteration"] = dev_ms / w["its"]
+    result["roofline"], result["cpu_baseline"] = roofline, cpu
     print(json.dumps(result), flush=True)
     return result
 
@@ -252,6 +289,7 @@ def bench_spatial_multi(args, world, rank, device):
     n_slabs, route = run.slabs()
     got = run.results()
     run.close()
+    dump_outputs(args.dump_outputs, got, bool(args.need_f))
     rows = holder.n_mvn_rows
     alg_bytes = (4 * T + 4 * rows + w["its"] * 6 * 8) * V
     ms = elapsed / args.steps * 1e3
@@ -268,7 +306,8 @@ def bench_spatial_multi(args, world, rank, device):
                            "achieved": alg_bytes / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS * (1 if rehearsal else world), "unit": "GB/s",
                            "frac": alg_bytes / (ms * 1e-3) / 1e9 / (HBM_PEAK_GBS * (1 if rehearsal else world)), "traffic": None,
                            "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": ms,
-                           "note": "wall time of one run on the host clock between barriers (several devices: no single stream to put events on)"},
+                           "note": "wall time of one run on the host clock between barriers (several devices: no single stream to put events on)"}
+                          if args.full else None,
               "cpu_baseline": None}
     print(json.dumps(result), flush=True)
     return result
@@ -423,6 +462,7 @@ def bench_single_process(args):
         for _ in range(args.steps):
             res = hiplib.run_spatial_host(holder, sp, y, devices=devices)
         elapsed = time.perf_counter() - t0
+        dump_outputs(args.dump_outputs, res, bool(args.need_f))
         result = {"metric": "voxels/sec to VB convergence", "value": V * args.steps / elapsed, "unit": "voxels/s", "n_gpus": n,
                   "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
                   "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -444,6 +484,7 @@ def bench_single_process(args):
     for _ in range(args.steps):
         res = hiplib.run_host(holder, y, devices=devices, into=res)
     elapsed = time.perf_counter() - t0
+    dump_outputs(args.dump_outputs, res, bool(args.need_f))
     s_f, s_it, bad = res["summary"]
     result = {"metric": "voxels/sec to VB convergence", "value": V * args.steps / elapsed, "unit": "voxels/s", "n_gpus": n,
               "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
@@ -467,16 +508,20 @@ def main():
     ap.add_argument("--grid", type=int, default=None, help="c5: side of the cubic volume (default 128)")
     ap.add_argument("--prior-type", default="M", choices=["M", "m", "P", "p"], help="c5: the spatial prior on amp1 (BASELINE config 5: M)")
     ap.add_argument("--need-f", action="store_true", help="also evaluate the free energy 4x per iteration (CLI default of the reference)")
-    ap.add_argument("--cpu-sample", type=int, default=32768, help="voxels timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=32768, help="with --full: voxels timed on the CPU oracle (0 = skip)")
     ap.add_argument("--variant", default="auto", choices=["auto", "lane", "wave"])
     ap.add_argument("--residual", default="auto", choices=["auto", "exact", "moments"],
                     help="how k'Qk is obtained (fabber_vb_set_residual_mode); default adaptive")
     ap.add_argument("--residual-tol", type=float, default=None)
-    ap.add_argument("--no-e2e", action="store_true", help="skip the timing of the host-pointer entry point and of the C ABI (the `e2e` object)")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the timing of the host-pointer entry point and of the C ABI (the `e2e` object)")
     ap.add_argument("--single-process", action="store_true",
                     help="with --gpus N: one process, the C++ engine's own sharding (fabber_vb_run_host_multi, host buffers: "
                          "the rate includes the PCIe transfers and is reported as such)")
     ap.add_argument("--e2e-child", action="store_true", help="(internal) measure the `e2e` object in this process and print it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the per-voxel outputs of the last timed step as DIR/<name>.npy (float64; a seeded sample above 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, CPU baseline (--cpu-sample) and the e2e child")
     args = ap.parse_args()
 
     if args.e2e_child:
@@ -559,12 +604,14 @@ def main():
         step()
     barrier()
     kernel_ms = []
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if args.full else []
     t0 = time.perf_counter()
     for i in range(args.steps):
-        ev[i][0].record()      # same stream the kernel is launched on (torch's current stream)
+        if ev:
+            ev[i][0].record()  # same stream the kernel is launched on (torch's current stream)
         prob.run()
-        ev[i][1].record()
+        if ev:
+            ev[i][1].record()
         summary[0] = prob.free_energy.sum() if args.need_f else prob.mvn[noise_row].sum()
         summary[1] = prob.iterations.sum(dtype=torch.float64)
         summary[2] = (prob.status != 0).sum(dtype=torch.float64)
@@ -577,12 +624,26 @@ def main():
 
     result = None
     if rank == 0:
+        got = prob.results() if args.dump_outputs or (args.full and args.cpu_sample > 0 and world == 1) else None
+        dump_outputs(args.dump_outputs, got, bool(args.need_f))
         total_voxels = V * world
         value = total_voxels * args.steps / elapsed
+        mean_its = summ[1] / (V * world)
+        result = {
+            "metric": "voxels/sec to VB convergence", "value": value, "unit": "voxels/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": w["desc"], "voxels_per_gpu": V, "total_voxels": total_voxels, "timepoints": T,
+                       "params": P, "iterations": w["its"], "need_f": bool(args.need_f), "parallelism": "voxel-shard x%d" % world,
+                       "input_dtype": "f32", "mean_iterations": mean_its, "bad_voxels": int(summ[2]),
+                       **({"rehearsal": "ranks share one GPU over gloo: not a measurement"} if rehearsal else {})},
+            "roofline": None, "cpu_baseline": None,
+        }
+    if rank == 0 and args.full:
         k_ms = float(np.mean(kernel_ms))
         rows = holder.n_mvn_rows
         alg_bytes = (4 * T + 4 * rows) * V
-        mean_its = summ[1] / (V * world)
         roofline = {
             "bound": "hbm", "kernel": prob.kernel,
             "achieved": alg_bytes / (k_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -613,7 +674,6 @@ def main():
             with ThreadPoolExecutor(ncores) as ex:
                 list(ex.map(lambda i: oracle.run(hs, ys, v_begin=int(edges[i]), v_end=int(edges[i + 1])), range(ncores)))
             cpu_all_s = time.perf_counter() - c0
-            got = prob.results()
             gpu = {k: (v[:, :ns] if v.ndim == 2 else v[:ns]) for k, v in got.items()}
             # Parity on the sample. The bi-exponential fit is chaotic: compare the
             # GPU-vs-CPU agreement with the agreement of two CPU builds of the same oracle source.
@@ -652,20 +712,11 @@ def main():
                    "posterior_mean_error_definition": "max over parameters+noise of |d mean| / max(|mean|, posterior sd), per voxel",
                    "gpu_vs_cpu": tolist(stats), "cpu_vs_cpu_fma_build_floor": tolist(floor),
                    "against_binary128_ground_truth": truth}
-        result = {
-            "metric": "voxels/sec to VB convergence", "value": value, "unit": "voxels/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": w["desc"], "voxels_per_gpu": V, "total_voxels": total_voxels, "timepoints": T,
-                       "params": P, "iterations": w["its"], "need_f": bool(args.need_f), "parallelism": "voxel-shard x%d" % world,
-                       "input_dtype": "f32", "mean_iterations": mean_its, "bad_voxels": int(summ[2]),
-                       **({"rehearsal": "ranks share one GPU over gloo: not a measurement"} if rehearsal else {})},
-            "roofline": roofline, "cpu_baseline": cpu,
-        }
+        result["roofline"], result["cpu_baseline"] = roofline, cpu
         if world == 1 and not args.no_e2e:
             # outside the timed region: the boundary's own rate (host pointers / the reference's C ABI)
             result["e2e"] = bench_boundary_in_child(args, V)
+    if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()

@@ -27,10 +27,10 @@ for w in c3 c3_needf c5; do
     cp gpurun_out/pmc_r3$w/trace/*/*kernel_stats.csv $OUT/r3_kernel_stats_$w.csv
     echo "[r3_profiles] $w done"
 done
-python3 bench.py --steps 20 --warmup 5 > $OUT/r3_bench_c3.json 2> $OUT/bench_c3.err
-python3 bench.py --steps 10 --need-f --cpu-sample 0 --no-e2e > $OUT/r3_bench_c3_needf.json 2>/dev/null
-python3 bench.py --steps 20 --workload c2 --no-e2e > $OUT/r3_bench_c2.json 2>/dev/null
-python3 bench.py --steps 10 --workload c4 --no-e2e > $OUT/r3_bench_c4.json 2>/dev/null
-python3 bench.py --steps 5 --workload c5 > $OUT/r3_bench_c5.json 2>/dev/null
-python3 bench.py --steps 5 --workload c1 --no-e2e > $OUT/r3_bench_c1.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/r3_bench_c3.json 2> $OUT/bench_c3.err
+python3 bench.py --full --steps 10 --need-f --cpu-sample 0 --no-e2e > $OUT/r3_bench_c3_needf.json 2>/dev/null
+python3 bench.py --full --steps 20 --workload c2 --no-e2e > $OUT/r3_bench_c2.json 2>/dev/null
+python3 bench.py --full --steps 10 --workload c4 --no-e2e > $OUT/r3_bench_c4.json 2>/dev/null
+python3 bench.py --full --steps 5 --workload c5 > $OUT/r3_bench_c5.json 2>/dev/null
+python3 bench.py --full --steps 5 --workload c1 --no-e2e > $OUT/r3_bench_c1.json 2>/dev/null
 echo "[r3_profiles] all done"

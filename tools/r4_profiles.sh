@@ -34,11 +34,11 @@ for w in ${WORKLOADS:-c3 c3_needf c5}; do
 done
 # bench.py reads profiles/r4_pmc_*.json: put this run's files there before the bench lines are taken
 cp $OUT/r4_pmc_c3.json $OUT/r4_pmc_c3_needf.json $OUT/r4_pmc_c5.json profiles/ 2>/dev/null
-python3 bench.py --steps 20 --warmup 5 > $OUT/r4_bench_c3.json 2> $OUT/bench_c3.err
-python3 bench.py --steps 20 --need-f --cpu-sample 0 --no-e2e > $OUT/r4_bench_c3_needf.json 2>/dev/null
-python3 bench.py --steps 20 --workload c2 --no-e2e > $OUT/r4_bench_c2.json 2>/dev/null
-python3 bench.py --steps 10 --workload c4 --no-e2e > $OUT/r4_bench_c4.json 2>/dev/null
-python3 bench.py --steps 10 --workload c5 > $OUT/r4_bench_c5.json 2>/dev/null
-python3 bench.py --steps 10 --workload c5 --prior-type P --cpu-sample 0 > $OUT/r4_bench_c5_typeP.json 2>/dev/null
-python3 bench.py --steps 5 --workload c1 --no-e2e > $OUT/r4_bench_c1.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/r4_bench_c3.json 2> $OUT/bench_c3.err
+python3 bench.py --full --steps 20 --need-f --cpu-sample 0 --no-e2e > $OUT/r4_bench_c3_needf.json 2>/dev/null
+python3 bench.py --full --steps 20 --workload c2 --no-e2e > $OUT/r4_bench_c2.json 2>/dev/null
+python3 bench.py --full --steps 10 --workload c4 --no-e2e > $OUT/r4_bench_c4.json 2>/dev/null
+python3 bench.py --full --steps 10 --workload c5 > $OUT/r4_bench_c5.json 2>/dev/null
+python3 bench.py --full --steps 10 --workload c5 --prior-type P --cpu-sample 0 > $OUT/r4_bench_c5_typeP.json 2>/dev/null
+python3 bench.py --full --steps 5 --workload c1 --no-e2e > $OUT/r4_bench_c1.json 2>/dev/null
 echo "[r4_profiles] all done"
