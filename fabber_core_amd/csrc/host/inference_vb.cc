@@ -792,7 +792,7 @@ void Vb::DoCalculations(FabberRunData &rundata)
         if (m_store->has_device_model && rc == -40)
         {
             // no spatial kernels were built for this model with this many parameters: the model's own host code
-            // does the re-centres instead (up to 8 parameters)
+            // does the re-centres instead (up to 32 parameters; more than 8 under white noise with one precision)
             LOG << "Vb::no device kernels for spatial VB with " << cfg.n_params << " parameters of this model" << endl;
             m_store->has_device_model = false;
             cfg.model = FVB_MODEL_HOSTJAC;

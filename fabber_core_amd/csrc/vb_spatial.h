@@ -1513,12 +1513,17 @@ struct SpatialKernels
     SpatialSweepFn slab_sweep[3]; // the ordered part, built for 1, 2 and up to P swept parameters (what a lane keeps in registers grows with it)
     int lds_classes;              // 1: setup / noise / noise_fast keep cfg.phi_index in LDS (n_times bytes of dynamic LDS)
     SpatialKernelFn noise_acc, noise_fast_acc; // the second sweep of the iterations that end in a pointwise re-centre, or NULL
+    // 1: the wave-per-voxel family (vb_spatial_wave.h): setup, theta and the second sweep launch ONE 64-lane workgroup
+    // per voxel with wave_lds bytes of dynamic LDS (a_K and pack keep the shapes above); 0: one lane per voxel
+    int wave;
+    size_t wave_lds;
 };
 SpatialKernels get_spatial_kernels_poly(int P, bool need_f);
 SpatialKernels get_spatial_kernels_linear(int P, bool need_f);
 SpatialKernels get_spatial_kernels_exp(int P, bool need_f);
 SpatialKernels get_spatial_kernels_more(int model, int P, bool need_f); // the larger parameter counts of the three above
 SpatialKernels get_spatial_kernels_host(int P, bool need_f); // models evaluated on the host (HostLinModel)
+SpatialKernels get_spatial_kernels_wide(int P, bool need_f); // ... with 1 <= P <= FVB_MAX_PARAMS, wave per voxel (vb_spatial_wave.hip)
 
 #if defined(__HIPCC__)
 template <class Model, int P, bool FAST>

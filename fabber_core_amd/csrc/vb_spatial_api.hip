@@ -457,6 +457,14 @@ static SpatialKernels spatial_kernels_for(const fvb_config *cfg)
         return SpatialKernels{};
     }
 }
+// what a configuration without a kernel table (-40) is told
+static std::string spatial_kernels_refusal(const fvb_config *cfg)
+{
+    if (cfg->model == FVB_MODEL_HOSTJAC && cfg->n_params > 8 && spatial_noise_kind(cfg) != FVB_SPNZ_WHITE)
+        return "spatial VB with more than 8 parameters runs white noise with one noise precision (noise patterns and AR(1) "
+               "noise: up to 6 parameters of a model evaluated on the host)";
+    return "no spatial kernel instantiation for this model / parameter count / noise model";
+}
 // entries of the noise block of the result MVN (WhiteParams / Ar1cParams::OutputAsMVN)
 static int spatial_noise_outputs(const fvb_config *cfg)
 {
@@ -556,7 +564,9 @@ int fvb_spatial_run::open(const fvb_config *cfg_, const fvb_spatial *sp_, const 
         return api_fail(-44, spatial_noise_refusal);
     k = spatial_kernels_for(&cfg);
     if (!k.setup)
-        return api_fail(-40, "no spatial kernel instantiation for this model / parameter count / noise model");
+        return api_fail(-40, spatial_kernels_refusal(&cfg));
+    if (cfg.model == FVB_MODEL_HOSTJAC && !lin_next) // (the kernels read the host's linearisations)
+        return api_fail(-56, "a model evaluated on the host runs spatial VB through fabber_vb_run_spatial_hostmodel_host");
     noise_lds = k.lds_classes ? (size_t)cfg.n_times : 0;
 
     // ---- Vb::SetupPerVoxelDists for every local voxel (ghosts included: their initial means are what the
@@ -605,7 +615,9 @@ int fvb_spatial_run::open(const fvb_config *cfg_, const fvb_spatial *sp_, const 
         // (the two buffers were allocated in `stream`'s order; the series is the caller's, complete in `stream`'s order too)
         FVB_HIP_CHECK(hipEventRecord(setup_done, stream));
         FVB_HIP_CHECK(hipStreamWaitEvent(setup_stream, setup_done, 0));
-        hipLaunchKernelGGL(k.setup, dim3((unsigned)((V + 63) / 64)), dim3(64), noise_lds, setup_stream, early);
+        // (the wave-per-voxel family: one workgroup per voxel)
+        hipLaunchKernelGGL(k.setup, dim3((unsigned)(k.wave ? V : (V + 63) / 64)), dim3(64), k.wave ? k.wave_lds : noise_lds,
+            setup_stream, early);
         FVB_HIP_CHECK(hipGetLastError());
         FVB_HIP_CHECK(hipEventRecord(setup_done, setup_stream));
     }
@@ -763,7 +775,8 @@ int fvb_spatial_run::open(const fvb_config *cfg_, const fvb_spatial *sp_, const 
         if (cfg.prior_type[kk] == FVB_PRIOR_SPATIAL_M || cfg.prior_type[kk] == FVB_PRIOR_SPATIAL_m)
             spatial_param[n_spatial++] = kk;
     const bool whole = owned_begin == 0 && owned_end == V;
-    const bool eligible = allow_fast && has_spatial && !minus_zero && (whole || multi_fast) && n_owned > 0 && !getenv("FVB_SPATIAL_PER_LEVEL");
+    const bool eligible = allow_fast && k.prep && has_spatial && !minus_zero && (whole || multi_fast) && n_owned > 0
+        && !getenv("FVB_SPATIAL_PER_LEVEL");
     std::vector<int32_t> pos_of, level_pos, level_count, slab_first;
     int n_pos = 0, sl_width = 64, sl_max_run = 0;
     slab_form = false;
@@ -1116,7 +1129,8 @@ int fvb_spatial_run::sweep_levels(int it, long long lo, long long hi)
         if (level_value[l] < lo || level_value[l] >= hi)
             continue;
         const int begin = level_begin[l], count = level_begin[l + 1] - level_begin[l];
-        hipLaunchKernelGGL(k.theta, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, stream, sap, begin, count, it);
+        hipLaunchKernelGGL(k.theta, dim3((unsigned)(k.wave ? count : (count + 63) / 64)), dim3(64), k.wave ? k.wave_lds : 0, stream,
+            sap, begin, count, it);
     }
     FVB_HIP_CHECK(hipGetLastError());
     return 0;
@@ -1127,7 +1141,8 @@ int fvb_spatial_run::sweep_noise(int it)
     sa.it = it;
     const int n_owned = owned_end - owned_begin;
     if (n_owned > 0)
-        hipLaunchKernelGGL(second_sweep(false, it), dim3((unsigned)((n_owned + 63) / 64)), dim3(64), noise_lds, stream, sa);
+        hipLaunchKernelGGL(second_sweep(false, it), dim3((unsigned)(k.wave ? n_owned : (n_owned + 63) / 64)), dim3(64),
+            k.wave ? k.wave_lds : noise_lds, stream, sa);
     FVB_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1600,7 +1615,7 @@ static int32_t run_spatial_host_impl(const fvb_config *cfg, const fvb_spatial *s
     if (spatial_noise_kind(cfg) < 0)
         return api_fail(-44, spatial_noise_refusal);
     if (!spatial_kernels_for(cfg).setup)
-        return api_fail(-40, "no spatial kernel instantiation for this model / parameter count / noise model");
+        return api_fail(-40, spatial_kernels_refusal(cfg));
     const int P = cfg->n_params;
     const int n = P + spatial_noise_outputs(cfg), rows = n * (n + 1) / 2 + n + 1;
     const size_t esz = cfg->data_f64 ? 8 : 4;

@@ -338,6 +338,95 @@ def run_spatial_host(holder, spatial, data, device=0, progress_cb=None, devices=
     return arrs
 
 
+def initial_mvn(holder, data):
+    """The initial posterior image [mvn_rows][V] of a holder, as Vb::BuildInitialMvn writes it for the routes that
+    evaluate the model on the host: the model's initial posterior in Fabber space (means from post_mean or the image
+    prior, variances from post_var, no covariances) and the noise posterior as its mean and variance. The exponential
+    model's InitVoxelPosterior sets amplitude i to max(y) / (num-exps + i) (examples/fwdmodel_exp.cc). White noise."""
+    cfg = holder.cfg
+    V, T, P = cfg.n_voxels, cfg.n_times, cfg.n_params
+    assert not cfg.params_ext and cfg.noise == vbabi.NOISE_WHITE
+    n = P + cfg.n_phis
+    nCov = n * (n + 1) // 2
+    img = np.zeros((vbabi.mvn_rows(n), V))
+    data_max = np.asarray(data, dtype=np.float64).max(axis=0) if cfg.model == vbabi.MODEL_EXP else None
+    for i in range(P):
+        tr = cfg.transform[i]
+        if cfg.prior_type[i] == vbabi.PRIOR_IMAGE:
+            mean = np.array(holder.keep["image_%d" % i], dtype=np.float64)
+        else:
+            mean = np.full(V, cfg.post_mean[i])
+        if data_max is not None and i % 2 == 0:
+            mean = data_max / (P // 2 + i // 2)
+        img[nCov + i] = [vbabi.to_fabber(tr, float(m)) for m in mean]
+        img[i * (i + 1) // 2 + i] = vbabi.to_fabber_var(tr, cfg.post_var[i])
+    for k in range(cfg.n_phis):
+        b, c = cfg.noise_post_b[k], cfg.noise_post_c[k]
+        q = P + k
+        img[q * (q + 1) // 2 + q] = b * b * c  # GammaDist variance / mean, as OutputAsMVN
+        img[nCov + q] = b * c
+    img[-1] = 1.0
+    return img
+
+
+def jacobian_callback(linearise, T, P):
+    """fvb_linearise_fn from a Python function that returns the linearisation itself: linearise(params [n][P] Fabber
+    space, voxel ids [n]) -> (g [n][T], J [n][T][P]) - a linear model hands over its design matrix exactly. Keep the
+    returned object alive for the duration of the call."""
+    def cb(user, n, ids, means, lin):
+        try:
+            v = np.ctypeslib.as_array(ids, (n,))
+            m = np.ctypeslib.as_array(means, (n * P,)).reshape(n, P)
+            out = np.ctypeslib.as_array(lin, (n * T * (P + 1),)).reshape(n, T * (P + 1))
+            g, J = linearise(m.copy(), v.copy())
+            out[:, :T] = np.broadcast_to(np.asarray(g, dtype=np.float64), (n, T))
+            out[:, T:] = np.broadcast_to(np.asarray(J, dtype=np.float64), (n, T, P)).reshape(n, -1)
+            return 0
+        except Exception:  # noqa: BLE001 (the engine reports -54)
+            return 1
+    return LINEARISE_FN(cb)
+
+
+def run_spatial_hostmodel_host(holder, spatial, data, linearise, device=0, progress_cb=None):
+    """Spatial VB with the model evaluated by the caller (fabber_vb_run_spatial_hostmodel_host): up to 8 parameters one
+    voxel per lane, 9 to 32 one wavefront per voxel (white noise with one precision). `linearise` is either what
+    recentre_callback(model, T, P) returns (the reference's central differences about the current means) or a Python
+    function for jacobian_callback (g and J directly). The initial posterior is the holder's init_mvn if it has one,
+    else initial_mvn(holder, data). The holder's model fields are not read. Returns the dict of run_spatial_host."""
+    cfg = holder.cfg
+    data = _prepare_data(holder, data)
+    V, T, P = cfg.n_voxels, cfg.n_times, cfg.n_params
+    cb = linearise if isinstance(linearise, LINEARISE_FN) else jacobian_callback(linearise, T, P)
+    init = None if cfg.init_mvn else np.ascontiguousarray(initial_mvn(holder, data))
+    arrs = dict(
+        mvn=np.full((holder.n_mvn_rows, V), np.nan),
+        free_energy=np.full(V, np.nan),
+        status=np.full(V, -1, dtype=np.int32),
+        iterations=np.full(V, -1, dtype=np.int32),
+    )
+    out = vbabi.FvbOutputs()
+    for k, a in arrs.items():
+        setattr(out, k, a.ctypes.data)
+    L = lib()
+    L.fabber_vb_run_spatial_hostmodel_host.restype = C.c_int32
+    L.fabber_vb_run_spatial_hostmodel_host.argtypes = [C.POINTER(vbabi.FvbConfig), C.POINTER(vbabi.FvbSpatial), C.c_void_p,
+                                                       C.POINTER(vbabi.FvbOutputs), C.c_int32, LINEARISE_FN, C.c_void_p,
+                                                       C.c_void_p]
+    pcb = PROGRESS_CB(progress_cb) if progress_cb else None
+    saved = (cfg.model, cfg.design, cfg.init_mvn)
+    cfg.model, cfg.design = vbabi.MODEL_HOSTJAC, None
+    if init is not None:
+        cfg.init_mvn = init.ctypes.data
+    try:
+        _check(L.fabber_vb_run_spatial_hostmodel_host(C.byref(cfg), C.byref(spatial.sp), data.ctypes.data, C.byref(out), device,
+                                                      cb, None, C.cast(pcb, C.c_void_p) if pcb else None))
+    finally:
+        cfg.model, cfg.design, cfg.init_mvn = saved
+    arrs["setup_failed"] = (arrs["status"] & 0x100) != 0
+    arrs["status"] = arrs["status"] & 0xFF
+    return arrs
+
+
 class SpatialMultiRun:
     """One spatial VB problem resident on several devices (fabber_vb_spatial_multi_*): open uploads, run() is one
     complete run on the resident data (may be repeated), results() downloads, close() frees."""

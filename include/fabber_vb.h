@@ -439,6 +439,9 @@ void fabber_vb_test_unlink_slab_pair(int32_t pair);
  * be complete on the host before the second sweep starts). Arguments as fabber_vb_run_spatial_host plus the
  * callback; cfg->init_mvn must hold the initial posterior. Device memory: two buffers of
  * n_voxels x n_times x (n_params + 1) doubles (-55 beyond 48 GB each).
+ * Parameter counts: up to 8 with one voxel per lane, under every noise model spatial VB takes (noise patterns and
+ * AR(1) noise up to 6); 9 to FVB_MAX_PARAMS (32) with one wavefront per voxel, white noise with one noise precision
+ * only (-40 otherwise). More than FVB_MAX_PARAMS: refused (-4).
  */
 int32_t fabber_vb_run_spatial_hostmodel_host(const fvb_config *cfg, const fvb_spatial *sp, const void *data, const fvb_outputs *out,
     int32_t device, fvb_linearise_fn linearise, void *user, void (*progress_cb)(int, int));
