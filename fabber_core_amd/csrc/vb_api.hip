@@ -6,7 +6,7 @@
  * negative code and fabber_vb_last_error() says why.
  */
 #include "vb_dispatch.h"
-#include "vb_host_copy.h"
+#include "vb_host_stage.h"
 #include "vb_wave_kernel.h"
 
 #include <hip/hip_runtime.h>
@@ -40,14 +40,6 @@ int fail(int code, const std::string &msg)
     g_last_error = msg;
     return code;
 }
-
-#define FVB_HIP_CHECK(expr)                                                                                  \
-    do                                                                                                       \
-    {                                                                                                        \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess)                                                                                \
-            return fail(-100 - (int)e_, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
-    } while (0)
 
 int noise_outputs(const fvb_config *cfg)
 {
@@ -202,16 +194,6 @@ bool needs_save(const fvb_config *cfg)
         || cfg->convergence == FVB_CONV_LM;
 }
 
-int count_unmasked(const fvb_config *cfg, const uint8_t *phi_index_host)
-{
-    if (!phi_index_host)
-        return cfg->n_times;
-    int n = 0;
-    for (int t = 0; t < cfg->n_times; t++)
-        n += (phi_index_host[t] != 255);
-    return n;
-}
-
 // ---- post-processing kernel: InferenceTechnique::SaveResults / Vb::SaveResults ----------------
 template <int MAXP>
 __global__ __launch_bounds__(256) void vb_postproc_kernel(
@@ -271,140 +253,6 @@ __global__ __launch_bounds__(256) void vb_postproc_kernel(
         }
     }
 }
-
-} // namespace
-namespace fvb
-{
-void api_keep_pool_memory();
-hipError_t api_pool_alloc(void **p, size_t bytes, hipStream_t stream);
-hipError_t api_pool_free(void *p, hipStream_t stream);
-}
-namespace
-{
-// RAII device buffer used only by the *_host entry points: from the device's stream-ordered pool, which keeps the
-// memory between calls (hipMalloc + hipFree of the series-sized buffers were ~20 of the 50 ms a call on 1e6 voxels
-// of the bi-exponential configuration took through host pointers)
-// Device memory of ONE block of the pipelined host entry point: plain hipMalloc'd buffers that stay with the call's cached
-// streams (PipeStreams) and are handed out again - to the block that takes the slot three blocks later, and to the next
-// call. No stream-ordered pool here: upload, fit and download streams and two host threads work on a call, and with ROCm
-// 7.2's runtime buffers taken from ONE pool by several streams came out overlapping - wrong results from the pipelined
-// call, right ones with plain hipMalloc in the same code (tools/measure/runtime_check.py, runtime_check_capi.py); ROCm 7.0's
-// runtime did not show it. A slot's buffers are reused only after the block that had them has been SEEN to finish.
-struct BlockSlot
-{
-    struct Buf
-    {
-        void *p;
-        size_t cap;
-        bool used;
-    };
-    std::vector<Buf> bufs;
-    hipError_t take(void **out, size_t bytes)
-    {
-        int best = -1;
-        for (size_t i = 0; i < bufs.size(); i++)
-            if (!bufs[i].used && bufs[i].cap >= bytes && (best < 0 || bufs[i].cap < bufs[(size_t)best].cap))
-                best = (int)i;
-        if (best < 0)
-        {
-            const size_t cap = (bytes + (1u << 20) - 1) & ~(size_t)((1u << 20) - 1);
-            void *p = nullptr;
-            const hipError_t e = hipMalloc(&p, cap);
-            if (e != hipSuccess)
-                return e;
-            bufs.push_back(Buf{ p, cap, false });
-            best = (int)bufs.size() - 1;
-        }
-        bufs[(size_t)best].used = true;
-        *out = bufs[(size_t)best].p;
-        return hipSuccess;
-    }
-    void reset()
-    {
-        for (Buf &b : bufs)
-            b.used = false;
-    }
-    void destroy()
-    {
-        for (Buf &b : bufs)
-            (void)hipFree(b.p);
-        bufs.clear();
-    }
-};
-
-struct DevBuf
-{
-    void *p = nullptr;
-    hipStream_t stream = nullptr;
-    BlockSlot *slot = nullptr; // the memory is the slot's (nothing to free here)
-    ~DevBuf()
-    {
-        if (p && !slot)
-            (void)fvb::api_pool_free(p, stream);
-    }
-    hipError_t alloc(size_t bytes, hipStream_t s = nullptr)
-    {
-        stream = s;
-        if (slot)
-            return slot->take(&p, bytes ? bytes : 8);
-        return fvb::api_pool_alloc(&p, bytes ? bytes : 8, s);
-    }
-};
-
-// A host fvb_param_table (fvb_config.params_ext: more than FVB_MAX_PARAMS parameters) on the device: the seven arrays,
-// the image priors of the voxels [v0, v0 + Vb) and the table itself
-struct DeviceParamTable
-{
-    DevBuf block;
-    std::vector<std::unique_ptr<DevBuf> > images;
-    const fvb_param_table *device = nullptr;
-    int upload(const fvb_config *cfg, size_t v0, size_t Vb, hipStream_t stream)
-    {
-        const fvb_param_table *h = cfg->params_ext;
-        const size_t P = (size_t)cfg->n_params, V = (size_t)cfg->n_voxels;
-        // [table][transform, prior_type: int32 P each][5 double arrays][image pointers]
-        const size_t off_i = sizeof(fvb_param_table), off_d = off_i + 2 * P * sizeof(int32_t) + (2 * P * sizeof(int32_t)) % 8;
-        const size_t off_p = off_d + 5 * P * sizeof(double), bytes = off_p + P * sizeof(double *);
-        std::vector<char> host(bytes, 0);
-        FVB_HIP_CHECK(block.alloc(bytes, stream));
-        char *dev = (char *)block.p;
-        fvb_param_table t;
-        t.transform = (const int32_t *)(dev + off_i);
-        t.prior_type = t.transform + P;
-        t.prior_mean = (const double *)(dev + off_d);
-        t.prior_var = t.prior_mean + P;
-        t.prior_prec = t.prior_var + P;
-        t.post_mean = t.prior_prec + P;
-        t.post_var = t.post_mean + P;
-        t.image_prior = (const double *const *)(dev + off_p);
-        memcpy(host.data(), &t, sizeof(t));
-        memcpy(host.data() + off_i, h->transform, P * sizeof(int32_t));
-        memcpy(host.data() + off_i + P * sizeof(int32_t), h->prior_type, P * sizeof(int32_t));
-        const double *src[5] = { h->prior_mean, h->prior_var, h->prior_prec, h->post_mean, h->post_var };
-        for (int a = 0; a < 5; a++)
-            memcpy(host.data() + off_d + (size_t)a * P * sizeof(double), src[a], P * sizeof(double));
-        const double **img = (const double **)(host.data() + off_p);
-        for (size_t k = 0; k < P; k++)
-        {
-            if (h->prior_type[k] < 0 || h->prior_type[k] > FVB_PRIOR_ARD)
-                return fail(-14, "a parameter table takes prior types N, I and ARD");
-            if (h->prior_type[k] == FVB_PRIOR_IMAGE && !(h->image_prior && h->image_prior[k]))
-                return fail(-13, "image prior without an image");
-            if (h->image_prior && h->image_prior[k])
-            {
-                images.emplace_back(new DevBuf);
-                FVB_HIP_CHECK(images.back()->alloc(sizeof(double) * Vb, stream));
-                FVB_HIP_CHECK(hipMemcpyAsync(images.back()->p, h->image_prior[k] + v0, sizeof(double) * Vb, hipMemcpyHostToDevice, stream));
-                img[k] = (const double *)images.back()->p;
-            }
-        }
-        (void)V;
-        FVB_HIP_CHECK(hipMemcpyAsync(block.p, host.data(), bytes, hipMemcpyHostToDevice, stream));
-        FVB_HIP_CHECK(hipStreamSynchronize(stream)); // (`host` is a local; the image priors are the caller's pageable memory)
-        device = (const fvb_param_table *)block.p;
-        return 0;
-    }
-};
 
 } // namespace
 
@@ -812,7 +660,7 @@ int32_t fabber_vb_run_device(const fvb_config *cfg, const void *data, const fvb_
         std::vector<uint8_t> h(cfg->n_times);
         FVB_HIP_CHECK(hipMemcpyAsync(h.data(), cfg->phi_index, h.size(), hipMemcpyDeviceToHost, (hipStream_t)stream));
         FVB_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-        n_unmasked = count_unmasked(cfg, h.data());
+        n_unmasked = count_unmasked((size_t)cfg->n_times, h.data());
     }
     return fabber_vb_run_device_ex(cfg, data, out, stream, n_unmasked);
 }
@@ -830,14 +678,8 @@ struct HostBlock
     const fvb_config *cfg = nullptr;
     const void *data = nullptr;
     const fvb_outputs *out = nullptr;
-    int v0 = 0, v1 = 0, kernel_voxels = 0, rows = 0;
-    fvb_config d;
-    fvb_outputs dout;
-    DevBuf b_data, b_design, b_phi, b_init, b_img[FVB_MAX_PARAMS], b_mvn, b_small, b_hist;
-    // F (8 bytes), history length, status, iterations (4 each) of a voxel: one device buffer, [F][hlen][status][it]
-    static constexpr size_t SMALL_BYTES_PER_VOXEL = 8 + 4 + 4 + 4;
-    size_t small_bytes = 0;
-    DeviceParamTable ptable;
+    int v0 = 0, v1 = 0, kernel_voxels = 0;
+    StagedProblem staged;
     hipEvent_t up_done = nullptr, fit_done = nullptr;
     BlockSlot *slot = nullptr; // pipelined entry point: where every device buffer of the block comes from
     ~HostBlock()
@@ -851,92 +693,10 @@ struct HostBlock
     }
     int stage_in(hipStream_t stream)
     {
-        const size_t V = (size_t)cfg->n_voxels, T = (size_t)cfg->n_times, Vb = (size_t)(v1 - v0);
-        const int P = cfg->n_params;
-        rows = fabber_vb_mvn_rows(P + noise_outputs(cfg));
-        const size_t esz = cfg->data_f64 ? 8 : 4;
-        auto upload = [&](void *dst, const void *src, size_t elem, size_t nrows) {
-            return copy_rows(dst, Vb * elem, (const char *)src + (size_t)v0 * elem, V * elem, Vb * elem, nrows, hipMemcpyHostToDevice,
-                stream);
-        };
-        d = *cfg;
-        d.n_voxels = (int32_t)Vb;
-        if (slot)
-        {
-            for (DevBuf *b : { &b_data, &b_design, &b_phi, &b_init, &b_mvn, &b_small, &b_hist })
-                b->slot = slot;
-            for (DevBuf &b : b_img)
-                b.slot = slot;
-        }
-        FVB_HIP_CHECK(b_data.alloc(T * Vb * esz, stream));
-        FVB_HIP_CHECK(upload(b_data.p, data, esz, T));
-        if (cfg->design)
-        {
-            FVB_HIP_CHECK(b_design.alloc(sizeof(double) * T * P, stream));
-            FVB_HIP_CHECK(hipMemcpyAsync(b_design.p, cfg->design, sizeof(double) * T * P, hipMemcpyHostToDevice, stream));
-            d.design = (const double *)b_design.p;
-        }
-        if (cfg->phi_index)
-        {
-            FVB_HIP_CHECK(b_phi.alloc(T, stream));
-            FVB_HIP_CHECK(hipMemcpyAsync(b_phi.p, cfg->phi_index, T, hipMemcpyHostToDevice, stream));
-            d.phi_index = (const uint8_t *)b_phi.p;
-        }
-        if (cfg->init_mvn)
-        {
-            FVB_HIP_CHECK(b_init.alloc(sizeof(double) * rows * Vb, stream));
-            FVB_HIP_CHECK(upload(b_init.p, cfg->init_mvn, sizeof(double), rows));
-            d.init_mvn = (const double *)b_init.p;
-        }
-        if (cfg->params_ext) // more than FVB_MAX_PARAMS parameters: the per-parameter entries as a table on the device
-        {
-            const int rc = ptable.upload(cfg, (size_t)v0, Vb, stream);
-            if (rc)
-                return rc;
-            d.params_ext = ptable.device;
-        }
-        for (int k = 0; k < P && !cfg->params_ext; k++)
-            if (cfg->image_prior[k])
-            {
-                FVB_HIP_CHECK(b_img[k].alloc(sizeof(double) * Vb, stream));
-                FVB_HIP_CHECK(upload(b_img[k].p, cfg->image_prior[k], sizeof(double), 1));
-                d.image_prior[k] = (const double *)b_img[k].p;
-            }
-        memset(&dout, 0, sizeof(dout));
-        FVB_HIP_CHECK(b_mvn.alloc(sizeof(double) * rows * Vb, stream));
-        dout.mvn = (double *)b_mvn.p;
-        {
-            // (sections the caller does not want are left out; every section starts on a multiple of 8 bytes because F
-            // comes first and Vb is even for every block but possibly the last, whose int sections are padded)
-            const size_t ints = (Vb + 1) / 2 * 2 * sizeof(int32_t);
-            small_bytes = (out->free_energy ? sizeof(double) * Vb : 0) + (out->f_history_len ? ints : 0) + (out->status ? ints : 0)
-                + (out->iterations ? ints : 0);
-            FVB_HIP_CHECK(b_small.alloc(small_bytes, stream));
-            char *q = (char *)b_small.p;
-            if (out->free_energy)
-            {
-                dout.free_energy = (double *)q;
-                q += sizeof(double) * Vb;
-            }
-            if (out->f_history_len)
-            {
-                dout.f_history_len = (int32_t *)q;
-                q += ints;
-            }
-            if (out->status)
-            {
-                dout.status = (int32_t *)q;
-                q += ints;
-            }
-            if (out->iterations)
-                dout.iterations = (int32_t *)q;
-        }
-        if (out->f_history && cfg->f_history_rows > 0)
-        {
-            FVB_HIP_CHECK(b_hist.alloc(sizeof(double) * cfg->f_history_rows * Vb, stream));
-            FVB_HIP_CHECK(hipMemsetAsync(b_hist.p, 0xff, sizeof(double) * cfg->f_history_rows * Vb, stream)); // NaN fill
-            dout.f_history = (double *)b_hist.p;
-        }
+        const int rc = staged.stage_in(cfg, data, out, (size_t)fabber_vb_mvn_rows(cfg->n_params + noise_outputs(cfg)), (size_t)v0, (size_t)v1,
+            stream, from_slot(slot), STAGE_VB);
+        if (rc)
+            return rc;
         FVB_HIP_CHECK(hipEventCreateWithFlags(&up_done, hipEventDisableTiming));
         FVB_HIP_CHECK(hipEventRecord(up_done, stream));
         return 0;
@@ -944,55 +704,18 @@ struct HostBlock
     int fit(hipStream_t stream, int n_unmasked)
     {
         FVB_HIP_CHECK(hipStreamWaitEvent(stream, up_done, 0));
-        int rc = run_device_as(&d, b_data.p, &dout, stream, n_unmasked, kernel_voxels, slot);
+        int rc = run_device_as(&staged.d, staged.b_data.p, &staged.dout, stream, n_unmasked, kernel_voxels, slot);
         if (rc)
             return rc;
         FVB_HIP_CHECK(hipEventCreateWithFlags(&fit_done, hipEventDisableTiming));
         FVB_HIP_CHECK(hipEventRecord(fit_done, stream));
         return 0;
     }
-    // returns after the block's results are in the caller's arrays. bounce: pinned host memory of at least small_bytes
-    // (the small arrays come down in one copy and are handed out from there), or NULL: one copy per array
+    // returns after the block's results are in the caller's arrays (bounce: see StagedProblem::stage_out)
     int stage_out(hipStream_t stream, void *bounce = nullptr)
     {
-        const size_t V = (size_t)cfg->n_voxels, Vb = (size_t)(v1 - v0);
-        auto download = [&](void *dst, const void *src, size_t elem, size_t nrows) {
-            return copy_rows((char *)dst + (size_t)v0 * elem, V * elem, src, Vb * elem, Vb * elem, nrows, hipMemcpyDeviceToHost, stream);
-        };
         FVB_HIP_CHECK(hipStreamWaitEvent(stream, fit_done, 0));
-        if (bounce && small_bytes)
-            FVB_HIP_CHECK(hipMemcpyAsync(bounce, b_small.p, small_bytes, hipMemcpyDeviceToHost, stream)); // (ahead of the big one)
-        FVB_HIP_CHECK(download(out->mvn, dout.mvn, sizeof(double), rows));
-        if (dout.f_history)
-            FVB_HIP_CHECK(download(out->f_history, dout.f_history, sizeof(double), cfg->f_history_rows));
-        if (!bounce)
-        {
-            if (dout.free_energy)
-                FVB_HIP_CHECK(download(out->free_energy, dout.free_energy, sizeof(double), 1));
-            if (dout.f_history_len)
-                FVB_HIP_CHECK(download(out->f_history_len, dout.f_history_len, sizeof(int32_t), 1));
-            if (dout.status)
-                FVB_HIP_CHECK(download(out->status, dout.status, sizeof(int32_t), 1));
-            if (dout.iterations)
-                FVB_HIP_CHECK(download(out->iterations, dout.iterations, sizeof(int32_t), 1));
-        }
-        FVB_HIP_CHECK(hipStreamSynchronize(stream));
-        if (bounce && small_bytes)
-        {
-            const char *base = (const char *)b_small.p;
-            auto hand_out = [&](void *dst, const void *dev, size_t elem) {
-                memcpy((char *)dst + (size_t)v0 * elem, (const char *)bounce + ((const char *)dev - base), Vb * elem);
-            };
-            if (dout.free_energy)
-                hand_out(out->free_energy, dout.free_energy, sizeof(double));
-            if (dout.f_history_len)
-                hand_out(out->f_history_len, dout.f_history_len, sizeof(int32_t));
-            if (dout.status)
-                hand_out(out->status, dout.status, sizeof(int32_t));
-            if (dout.iterations)
-                hand_out(out->iterations, dout.iterations, sizeof(int32_t));
-        }
-        return 0;
+        return staged.stage_out(out, stream, bounce);
     }
 };
 
@@ -1011,7 +734,7 @@ int run_host_block(const fvb_config *cfg, const void *data, const fvb_outputs *o
     b.kernel_voxels = kernel_voxels;
     int rc = b.stage_in(stream);
     if (rc == 0)
-        rc = b.fit(stream, count_unmasked(cfg, cfg->phi_index));
+        rc = b.fit(stream, count_unmasked((size_t)cfg->n_times, cfg->phi_index));
     if (rc == 0)
         rc = b.stage_out(stream);
     if (rc)
@@ -1168,7 +891,7 @@ int run_host_pipelined(const fvb_config *cfg, const void *data, const fvb_output
                 bounds.push_back(std::min(V, v));
     }
     const int n_blocks = (int)bounds.size() - 1;
-    const int n_unmasked = count_unmasked(cfg, cfg->phi_index);
+    const int n_unmasked = count_unmasked((size_t)cfg->n_times, cfg->phi_index);
     // (two streams take the blocks' kernels in turn: the first wavefronts of block b + 1 move into the SIMDs the last
     // stragglers of block b have left, instead of every block paying for its own tail)
     PipeStreams ps;
@@ -1184,7 +907,7 @@ int run_host_pipelined(const fvb_config *cfg, const void *data, const fvb_output
         int widest = 0;
         for (int b = 0; b < n_blocks; b++)
             widest = std::max(widest, bounds[(size_t)b + 1] - bounds[(size_t)b]);
-        const int rc_bounce = ps.need_bounce((size_t)widest * HostBlock::SMALL_BYTES_PER_VOXEL + 64);
+        const int rc_bounce = ps.need_bounce((size_t)widest * StagedProblem::SMALL_BYTES_PER_VOXEL + 64);
         if (rc_bounce)
         {
             ps.destroy();
@@ -1444,7 +1167,7 @@ int32_t fabber_vb_postproc_host(const fvb_config *cfg, const void *data, const d
     const int rows = fabber_vb_mvn_rows(P + N);
     const size_t esz = cfg->data_f64 ? 8 : 4;
     fvb_config d = *cfg;
-    DevBuf b_data, b_design, b_mvn;
+    DevMem b_data, b_design, b_mvn;
     DeviceParamTable ptable;
     if (cfg->params_ext)
     {
@@ -1458,15 +1181,12 @@ int32_t fabber_vb_postproc_host(const fvb_config *cfg, const void *data, const d
             return rc;
         d.params_ext = ptable.device;
     }
-    if (data)
-    {
-        FVB_HIP_CHECK(b_data.alloc(T * V * esz));
-        FVB_HIP_CHECK(hipMemcpy(b_data.p, data, T * V * esz, hipMemcpyHostToDevice));
-    }
+    if (data && (rc = upload_array(b_data, data, T * V * esz, nullptr)) != 0)
+        return rc;
     if (cfg->design)
     {
-        FVB_HIP_CHECK(b_design.alloc(sizeof(double) * T * P));
-        FVB_HIP_CHECK(hipMemcpy(b_design.p, cfg->design, sizeof(double) * T * P, hipMemcpyHostToDevice));
+        if ((rc = upload_array(b_design, cfg->design, sizeof(double) * T * P, nullptr)) != 0)
+            return rc;
         d.design = (const double *)b_design.p;
     }
     FVB_HIP_CHECK(b_mvn.alloc(sizeof(double) * rows * V));
@@ -1498,7 +1218,7 @@ int32_t fabber_vb_postproc_host(const fvb_config *cfg, const void *data, const d
         { &pp->std, &dpp.std, (size_t)P }, { &pp->zstat, &dpp.zstat, (size_t)P }, { &pp->modelfit, &dpp.modelfit, T },
         { &pp->residuals, &dpp.residuals, T }, { &pp->noise_mean, &dpp.noise_mean, (size_t)N },
         { &pp->noise_std, &dpp.noise_std, (size_t)N } };
-    DevBuf bufs[8];
+    DevMem bufs[8];
     for (int i = 0; i < 8; i++)
         if (*items[i].host)
         {

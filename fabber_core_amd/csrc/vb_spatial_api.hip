@@ -4,7 +4,7 @@
  * (inference_vb.cc:605-725) as a sequence of launches on one stream. See vb_spatial.h.
  */
 #include "vb_spatial_noise.h"
-#include "vb_host_copy.h"
+#include "vb_host_stage.h"
 
 #include <hip/hip_runtime.h>
 
@@ -24,29 +24,8 @@
 using namespace fvb;
 
 extern "C" const char *fabber_vb_last_error(void);
-namespace fvb
-{
-int api_fail(int code, const std::string &msg); // vb_api.hip
-int api_validate(const fvb_config *cfg, bool allow_spatial);
-int api_residual_mode();
-int api_precise_passes();
-double api_residual_tol();
-void api_keep_pool_memory();
-hipError_t api_pool_alloc(void **p, size_t bytes, hipStream_t stream);
-hipError_t api_take_side_stream(hipStream_t *out, int *device);
-void api_return_side_stream(hipStream_t s, int device);
-}
-
 namespace
 {
-#define FVB_HIP_CHECK(expr)                                                                                  \
-    do                                                                                                       \
-    {                                                                                                        \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess)                                                                                \
-            return api_fail(-100 - (int)e_, std::string(#expr) + ": " + hipGetErrorString(e_));              \
-    } while (0)
-
 int sign_of(int x)
 {
     return (x > 0) - (x < 0);
@@ -181,52 +160,6 @@ std::string build_neighbours(const int32_t *coords, int V, int dims, std::vector
         }
     return "";
 }
-
-// Device memory from the device's stream-ordered pool. The pool keeps what a run gives back (release threshold
-// set to "never" the first time), so a caller that runs volume after volume pays for its ~20 allocations once:
-// 4 ms per run of the 128^3 configuration with hipMalloc / hipFree.
-struct DevMem
-{
-    void *p = nullptr;
-    hipStream_t stream = nullptr;
-    bool plain = false; // hipMalloc'ed (fine-grained memory another device writes into), not from the pool
-    bool fine = false;  // ... and really fine-grained (alloc_fine falls back to ordinary device memory)
-    ~DevMem()
-    {
-        reset();
-    }
-    void reset()
-    {
-        if (p && plain)
-            (void)hipFree(p);
-        else if (p)
-            (void)hipFreeAsync(p, stream);
-        p = nullptr;
-        plain = false;
-        fine = false;
-    }
-    // memory that a kernel on ANOTHER device writes while a kernel on this one polls it (the inboxes of the slab sweep
-    // across devices): fine-grained, i.e. not held in this device's L2 between the polls
-    hipError_t alloc_fine(size_t bytes)
-    {
-        plain = true;
-        hipError_t e = hipExtMallocWithFlags(&p, bytes ? bytes : 8, hipDeviceMallocFinegrained);
-        fine = (e == hipSuccess);
-        if (e != hipSuccess)
-        {
-            // ordinary device memory: good for slabs that share a device; across devices a remote store might stay
-            // invisible to the polling device's L2, so the caller takes the level-chunk pipeline then (gran_fine)
-            (void)hipGetLastError();
-            e = hipMalloc(&p, bytes ? bytes : 8);
-        }
-        return e;
-    }
-    hipError_t alloc(size_t bytes, hipStream_t s = nullptr)
-    {
-        stream = s;
-        return fvb::api_pool_alloc(&p, bytes ? bytes : 8, s);
-    }
-};
 
 // ---- the same table built on the device -----------------------------------------------------------
 // For the usual geometry (non-negative co-ordinates, a mask that fills a fair share of its bounding
@@ -1429,8 +1362,35 @@ int run_spatial(const fvb_config *cfg, const fvb_spatial *sp, const void *d_data
 
 extern "C" {
 
+// the argument checks of the device entry points
+static int32_t spatial_check_args(const fvb_config *cfg, const fvb_spatial *sp, const fvb_outputs *out)
+{
+    int rc = api_validate(cfg, true);
+    if (rc)
+        return rc;
+    if (!sp || !sp->coords)
+        return api_fail(-42, "spatial description / coordinates missing");
+    if (sp->spatial_dims < 0 || sp->spatial_dims > 3)
+        return api_fail(-43, "spatial-dims must be 0, 1, 2 or 3");
+    if (spatial_noise_kind(cfg) < 0)
+        return api_fail(-44, spatial_noise_refusal);
+    if (!out || !out->mvn)
+        return api_fail(-20, "outputs.mvn is required");
+    return 0;
+}
+
 static int32_t run_spatial_checked(const fvb_config *cfg, const fvb_spatial *sp, const void *data, const fvb_outputs *out, void *stream,
-    void (*progress_cb)(int, int), HostLin *hl);
+    void (*progress_cb)(int, int), HostLin *hl)
+{
+    int rc = spatial_check_args(cfg, sp, out);
+    if (rc)
+        return rc;
+    if (cfg->n_voxels == 0)
+        return 0;
+    if (!data)
+        return api_fail(-21, "data is NULL");
+    return run_spatial(cfg, sp, data, out, (hipStream_t)stream, progress_cb, true, hl);
+}
 
 int32_t fabber_vb_run_spatial_device(const fvb_config *cfg, const fvb_spatial *sp, const void *data,
     const fvb_outputs *out, void *stream, void (*progress_cb)(int, int))
@@ -1440,44 +1400,15 @@ int32_t fabber_vb_run_spatial_device(const fvb_config *cfg, const fvb_spatial *s
     return run_spatial_checked(cfg, sp, data, out, stream, progress_cb, nullptr);
 }
 
-static int32_t run_spatial_checked(const fvb_config *cfg, const fvb_spatial *sp, const void *data, const fvb_outputs *out, void *stream,
-    void (*progress_cb)(int, int), HostLin *hl)
-{
-    int rc = api_validate(cfg, true);
-    if (rc)
-        return rc;
-    if (!sp || !sp->coords)
-        return api_fail(-42, "spatial description / coordinates missing");
-    if (sp->spatial_dims < 0 || sp->spatial_dims > 3)
-        return api_fail(-43, "spatial-dims must be 0, 1, 2 or 3");
-    if (spatial_noise_kind(cfg) < 0)
-        return api_fail(-44, spatial_noise_refusal);
-    if (!out || !out->mvn)
-        return api_fail(-20, "outputs.mvn is required");
-    if (cfg->n_voxels == 0)
-        return 0;
-    if (!data)
-        return api_fail(-21, "data is NULL");
-    return run_spatial(cfg, sp, data, out, (hipStream_t)stream, progress_cb, true, hl);
-}
-
 int32_t fabber_vb_spatial_open(const fvb_config *cfg, const fvb_spatial *sp, const void *data, const fvb_outputs *out,
     void *stream, fvb_spatial_run **run)
 {
     if (!run)
         return api_fail(-47, "run handle pointer is NULL");
     *run = nullptr;
-    int rc = api_validate(cfg, true);
+    int rc = spatial_check_args(cfg, sp, out);
     if (rc)
         return rc;
-    if (!sp || !sp->coords)
-        return api_fail(-42, "spatial description / coordinates missing");
-    if (sp->spatial_dims < 0 || sp->spatial_dims > 3)
-        return api_fail(-43, "spatial-dims must be 0, 1, 2 or 3");
-    if (spatial_noise_kind(cfg) < 0)
-        return api_fail(-44, spatial_noise_refusal);
-    if (!out || !out->mvn)
-        return api_fail(-20, "outputs.mvn is required");
     if (cfg->n_voxels == 0 || !data)
         return api_fail(-21, "no voxels / data is NULL");
     fvb_spatial_run *r = new fvb_spatial_run();
@@ -1560,7 +1491,47 @@ int32_t fabber_vb_spatial_close(fvb_spatial_run *run)
 }
 
 static int32_t run_spatial_host_impl(const fvb_config *cfg, const fvb_spatial *sp, const void *data, const fvb_outputs *out,
-    int32_t device, void (*progress_cb)(int, int), HostLin *hl);
+    int32_t device, void (*progress_cb)(int, int), HostLin *hl)
+{
+    int rc = api_validate(cfg, true);
+    if (rc)
+        return rc;
+    if (!out || !out->mvn)
+        return api_fail(-20, "outputs.mvn is required");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return api_fail(-30, "no HIP device available (the VB engine has no CPU fallback)");
+    FVB_HIP_CHECK(hipSetDevice(device));
+    const size_t V = (size_t)cfg->n_voxels;
+    if (V == 0)
+        return 0;
+    // (before anything is uploaded: a caller that falls back to the host-evaluated route on -40 has not paid for the
+    // series on the device twice)
+    if (spatial_noise_kind(cfg) < 0)
+        return api_fail(-44, spatial_noise_refusal);
+    if (!spatial_kernels_for(cfg).setup)
+        return api_fail(-40, spatial_kernels_refusal(cfg));
+    const int P = cfg->n_params;
+    const int n = P + spatial_noise_outputs(cfg), rows = n * (n + 1) / 2 + n + 1;
+    StagedProblem staged;
+    if ((rc = staged.stage_in(cfg, data, out, (size_t)rows, 0, V, nullptr, from_pool(), STAGE_SPATIAL)) != 0)
+        return rc;
+    if (staged.dout.free_energy) // NaN: a voxel that fails before any F is evaluated keeps it
+        FVB_HIP_CHECK(hipMemset(staged.dout.free_energy, 0xff, sizeof(double) * V));
+    fvb_spatial dsp = *sp;
+    DevMem b_locked;
+    if (sp->locked_centres)
+    {
+        if ((rc = upload_array(b_locked, sp->locked_centres, sizeof(double) * P * V, nullptr)) != 0)
+            return rc;
+        dsp.locked_centres = (const double *)b_locked.p;
+    }
+    rc = run_spatial_checked(&staged.d, &dsp, staged.b_data.p, &staged.dout, nullptr, progress_cb, hl);
+    if (rc)
+        return rc;
+    FVB_HIP_CHECK(hipDeviceSynchronize());
+    return staged.stage_out(out, nullptr);
+}
 
 int32_t fabber_vb_run_spatial_host(const fvb_config *cfg, const fvb_spatial *sp, const void *data,
     const fvb_outputs *out, int32_t device, void (*progress_cb)(int, int))
@@ -1595,101 +1566,6 @@ int32_t fabber_vb_run_spatial_hostmodel_host(const fvb_config *cfg, const fvb_sp
     return run_spatial_host_impl(cfg, sp, data, out, device, progress_cb, &hl);
 }
 
-static int32_t run_spatial_host_impl(const fvb_config *cfg, const fvb_spatial *sp, const void *data, const fvb_outputs *out,
-    int32_t device, void (*progress_cb)(int, int), HostLin *hl)
-{
-    int rc = api_validate(cfg, true);
-    if (rc)
-        return rc;
-    if (!out || !out->mvn)
-        return api_fail(-20, "outputs.mvn is required");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return api_fail(-30, "no HIP device available (the VB engine has no CPU fallback)");
-    FVB_HIP_CHECK(hipSetDevice(device));
-    const size_t V = (size_t)cfg->n_voxels, T = (size_t)cfg->n_times;
-    if (V == 0)
-        return 0;
-    // (before anything is uploaded: a caller that falls back to the host-evaluated route on -40 has not paid for the
-    // series on the device twice)
-    if (spatial_noise_kind(cfg) < 0)
-        return api_fail(-44, spatial_noise_refusal);
-    if (!spatial_kernels_for(cfg).setup)
-        return api_fail(-40, spatial_kernels_refusal(cfg));
-    const int P = cfg->n_params;
-    const int n = P + spatial_noise_outputs(cfg), rows = n * (n + 1) / 2 + n + 1;
-    const size_t esz = cfg->data_f64 ? 8 : 4;
-    fvb_config d = *cfg;
-    DevMem b_data, b_design, b_phi, b_init, b_img[FVB_MAX_PARAMS], b_mvn, b_f, b_status, b_it;
-    FVB_HIP_CHECK(b_data.alloc(T * V * esz));
-    FVB_HIP_CHECK(hipMemcpy(b_data.p, data, T * V * esz, hipMemcpyHostToDevice));
-    if (cfg->design)
-    {
-        FVB_HIP_CHECK(b_design.alloc(sizeof(double) * T * P));
-        FVB_HIP_CHECK(hipMemcpy(b_design.p, cfg->design, sizeof(double) * T * P, hipMemcpyHostToDevice));
-        d.design = (const double *)b_design.p;
-    }
-    if (cfg->phi_index)
-    {
-        FVB_HIP_CHECK(b_phi.alloc(T));
-        FVB_HIP_CHECK(hipMemcpy(b_phi.p, cfg->phi_index, T, hipMemcpyHostToDevice));
-        d.phi_index = (const uint8_t *)b_phi.p;
-    }
-    if (cfg->init_mvn)
-    {
-        FVB_HIP_CHECK(b_init.alloc(sizeof(double) * rows * V));
-        FVB_HIP_CHECK(hipMemcpy(b_init.p, cfg->init_mvn, sizeof(double) * rows * V, hipMemcpyHostToDevice));
-        d.init_mvn = (const double *)b_init.p;
-    }
-    for (int kk = 0; kk < P; kk++)
-        if (cfg->image_prior[kk])
-        {
-            FVB_HIP_CHECK(b_img[kk].alloc(sizeof(double) * V));
-            FVB_HIP_CHECK(hipMemcpy(b_img[kk].p, cfg->image_prior[kk], sizeof(double) * V, hipMemcpyHostToDevice));
-            d.image_prior[kk] = (const double *)b_img[kk].p;
-        }
-    fvb_outputs dout;
-    memset(&dout, 0, sizeof(dout));
-    FVB_HIP_CHECK(b_mvn.alloc(sizeof(double) * rows * V));
-    dout.mvn = (double *)b_mvn.p;
-    if (out->free_energy)
-    {
-        FVB_HIP_CHECK(b_f.alloc(sizeof(double) * V));
-        FVB_HIP_CHECK(hipMemset(b_f.p, 0xff, sizeof(double) * V)); // NaN: a voxel that fails before any F is evaluated keeps it
-        dout.free_energy = (double *)b_f.p;
-    }
-    if (out->status)
-    {
-        FVB_HIP_CHECK(b_status.alloc(sizeof(int32_t) * V));
-        dout.status = (int32_t *)b_status.p;
-    }
-    if (out->iterations)
-    {
-        FVB_HIP_CHECK(b_it.alloc(sizeof(int32_t) * V));
-        dout.iterations = (int32_t *)b_it.p;
-    }
-    fvb_spatial dsp = *sp;
-    DevMem b_locked;
-    if (sp->locked_centres)
-    {
-        FVB_HIP_CHECK(b_locked.alloc(sizeof(double) * P * V));
-        FVB_HIP_CHECK(hipMemcpy(b_locked.p, sp->locked_centres, sizeof(double) * P * V, hipMemcpyHostToDevice));
-        dsp.locked_centres = (const double *)b_locked.p;
-    }
-    rc = run_spatial_checked(&d, &dsp, b_data.p, &dout, nullptr, progress_cb, hl);
-    if (rc)
-        return rc;
-    FVB_HIP_CHECK(hipDeviceSynchronize());
-    FVB_HIP_CHECK(hipMemcpy(out->mvn, dout.mvn, sizeof(double) * rows * V, hipMemcpyDeviceToHost));
-    if (dout.free_energy)
-        FVB_HIP_CHECK(hipMemcpy(out->free_energy, dout.free_energy, sizeof(double) * V, hipMemcpyDeviceToHost));
-    if (dout.status)
-        FVB_HIP_CHECK(hipMemcpy(out->status, dout.status, sizeof(int32_t) * V, hipMemcpyDeviceToHost));
-    if (dout.iterations)
-        FVB_HIP_CHECK(hipMemcpy(out->iterations, dout.iterations, sizeof(int32_t) * V, hipMemcpyDeviceToHost));
-    return 0;
-}
-
 // ---- spatial VB of one volume on several devices, driven by this one process ---------------------------------
 // The decomposition and the schedule of fabber_core_amd/spatial_mgpu.py (one process per GPU over
 // torch.distributed) inside the engine: z-slabs with ghost planes, the first sweep as a pipeline over chunks
@@ -1704,21 +1580,18 @@ struct SlabRun
 {
     int dev = 0, g0 = 0, b = 0, e = 0, g1 = 0; // local list = global voxels [g0, g1), owned [b, e)
     hipStream_t stream = nullptr;
-    fvb_config d;
+    StagedProblem staged; // its part of the problem: the local list
     fvb_spatial sp;
-    fvb_outputs dout;
     std::vector<int32_t> coords;
-    DevMem b_data, b_design, b_phi, b_init, b_img[FVB_MAX_PARAMS], b_mvn, b_f, b_status, b_it, stage_means, stage_status;
+    DevMem stage_means, stage_status;
     fvb_spatial_run *run = nullptr;
     ~SlabRun()
     {
         (void)hipSetDevice(dev);
         delete run; // (its buffers go back to this device's pool in its stream's order)
-        DevMem *mine[] = { &b_data, &b_design, &b_phi, &b_init, &b_mvn, &b_f, &b_status, &b_it, &stage_means, &stage_status };
-        for (DevMem *m : mine) // ... and this slab's, before the stream they are ordered on goes
-            m->reset();
-        for (DevMem &m : b_img)
-            m.reset();
+        staged.release(); // ... and this slab's, before the stream they are ordered on goes
+        stage_means.reset();
+        stage_status.reset();
         if (stream)
         {
             (void)hipStreamSynchronize(stream);
@@ -1761,8 +1634,7 @@ struct fvb_spatial_multi
     std::vector<int32_t> coords; // (a copy: sp.coords points here)
     std::vector<int> devs;
     int V = 0, T = 0, P = 0, world = 0, halo = 1, rows = 0, max_halo = 1;
-    bool second = false, has_spatial = false, peers = true, want_f = false;
-    size_t esz = 4;
+    bool second = false, has_spatial = false, peers = true;
     std::vector<std::unique_ptr<SlabRun> > slabs;
     const char *route = "";
     double ms_open = 0, ms_setup = 0, ms_loop = 0;
@@ -1919,7 +1791,6 @@ int fvb_spatial_multi::plan(const fvb_config *cfg_, const fvb_spatial *sp_, cons
     }
     const int n = P + spatial_noise_outputs(&cfg);
     rows = n * (n + 1) / 2 + n + 1;
-    esz = cfg.data_f64 ? 8 : 4;
     max_halo = 1;
     for (int r = 0; r < (int)slabs.size(); r++)
         max_halo = std::max(max_halo, std::max(slabs[r]->b - slabs[r]->g0, slabs[r]->g1 - slabs[r]->e));
@@ -1929,65 +1800,15 @@ int fvb_spatial_multi::plan(const fvb_config *cfg_, const fvb_spatial *sp_, cons
 // ---- per slab: its part of the problem on its device (a host thread per slab: the devices work side by side) ----
 int fvb_spatial_multi::upload(const void *data, const fvb_outputs *out)
 {
-    want_f = out->free_energy != nullptr;
-    const bool want_status = out->status != nullptr, want_it = out->iterations != nullptr;
     auto upload_slab = [&](int r) -> int {
         SlabRun &sl = *slabs[r];
-        const size_t Vl = (size_t)(sl.g1 - sl.g0);
         FVB_HIP_CHECK(hipSetDevice(sl.dev));
         FVB_HIP_CHECK(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
         hipStream_t st = sl.stream;
-        auto upload_rows = [&](void *dst, const void *src, size_t elem, size_t nrows) {
-            return copy_rows(dst, Vl * elem, (const char *)src + (size_t)sl.g0 * elem, (size_t)V * elem, Vl * elem, nrows,
-                hipMemcpyHostToDevice, st);
-        };
-        sl.d = cfg;
-        sl.d.n_voxels = (int32_t)Vl;
-        FVB_HIP_CHECK(sl.b_data.alloc((size_t)T * Vl * esz, st));
-        FVB_HIP_CHECK(upload_rows(sl.b_data.p, data, esz, (size_t)T));
-        if (cfg.design)
-        {
-            FVB_HIP_CHECK(sl.b_design.alloc(sizeof(double) * (size_t)T * P, st));
-            FVB_HIP_CHECK(hipMemcpyAsync(sl.b_design.p, cfg.design, sizeof(double) * (size_t)T * P, hipMemcpyHostToDevice, st));
-            sl.d.design = (const double *)sl.b_design.p;
-        }
-        if (cfg.phi_index)
-        {
-            FVB_HIP_CHECK(sl.b_phi.alloc((size_t)T, st));
-            FVB_HIP_CHECK(hipMemcpyAsync(sl.b_phi.p, cfg.phi_index, (size_t)T, hipMemcpyHostToDevice, st));
-            sl.d.phi_index = (const uint8_t *)sl.b_phi.p;
-        }
-        if (cfg.init_mvn)
-        {
-            FVB_HIP_CHECK(sl.b_init.alloc(sizeof(double) * rows * Vl, st));
-            FVB_HIP_CHECK(upload_rows(sl.b_init.p, cfg.init_mvn, sizeof(double), (size_t)rows));
-            sl.d.init_mvn = (const double *)sl.b_init.p;
-        }
-        for (int k = 0; k < P; k++)
-            if (cfg.image_prior[k])
-            {
-                FVB_HIP_CHECK(sl.b_img[k].alloc(sizeof(double) * Vl, st));
-                FVB_HIP_CHECK(upload_rows(sl.b_img[k].p, cfg.image_prior[k], sizeof(double), 1));
-                sl.d.image_prior[k] = (const double *)sl.b_img[k].p;
-            }
-        memset(&sl.dout, 0, sizeof(sl.dout));
-        FVB_HIP_CHECK(sl.b_mvn.alloc(sizeof(double) * rows * Vl, st));
-        sl.dout.mvn = (double *)sl.b_mvn.p;
-        if (want_f)
-        {
-            FVB_HIP_CHECK(sl.b_f.alloc(sizeof(double) * Vl, st));
-            sl.dout.free_energy = (double *)sl.b_f.p;
-        }
-        if (want_status)
-        {
-            FVB_HIP_CHECK(sl.b_status.alloc(sizeof(int32_t) * Vl, st));
-            sl.dout.status = (int32_t *)sl.b_status.p;
-        }
-        if (want_it)
-        {
-            FVB_HIP_CHECK(sl.b_it.alloc(sizeof(int32_t) * Vl, st));
-            sl.dout.iterations = (int32_t *)sl.b_it.p;
-        }
+        const size_t Vl = (size_t)(sl.g1 - sl.g0);
+        const int rc = sl.staged.stage_in(&cfg, data, out, (size_t)rows, (size_t)sl.g0, (size_t)sl.g1, st, from_pool(), STAGE_SPATIAL);
+        if (rc)
+            return rc;
         FVB_HIP_CHECK(sl.stage_means.alloc(sizeof(double) * (size_t)P * max_halo, st));
         FVB_HIP_CHECK(sl.stage_status.alloc(sizeof(int32_t) * (size_t)max_halo, st));
         FVB_HIP_CHECK(hipStreamSynchronize(st)); // (the uploads read pageable host memory)
@@ -2033,12 +1854,12 @@ int fvb_spatial_multi::execute(void (*progress_cb)(int, int), bool no_fast)
         FVB_HIP_CHECK(hipSetDevice(sl.dev));
         delete sl.run;
         sl.run = nullptr;
-        if (sl.dout.free_energy)
-            FVB_HIP_CHECK(hipMemsetAsync(sl.b_f.p, 0xff, sizeof(double) * (size_t)(sl.g1 - sl.g0), sl.stream)); // NaN (see fabber_vb_run_spatial_host)
+        if (sl.staged.dout.free_energy)
+            FVB_HIP_CHECK(hipMemsetAsync(sl.staged.dout.free_energy, 0xff, sizeof(double) * (size_t)(sl.g1 - sl.g0), sl.stream)); // NaN (see fabber_vb_run_spatial_host)
         sl.run = new fvb_spatial_run;
         sl.run->allow_fast = sl.run->multi_fast = try_fast;
         sl.run->device_share = (int)std::count(devs.begin(), devs.begin() + world, sl.dev);
-        return sl.run->open(&sl.d, &sl.sp, sl.b_data.p, &sl.dout, sl.stream);
+        return sl.run->open(&sl.staged.d, &sl.sp, sl.staged.b_data.p, &sl.staged.dout, sl.stream);
     };
     if ((rc = for_each_slab(open_slab)) != 0)
         return rc;
@@ -2283,19 +2104,9 @@ int fvb_spatial_multi::download(const fvb_outputs *out)
     {
         SlabRun &sl = *slabs[r];
         FVB_HIP_CHECK(hipSetDevice(sl.dev));
-        const size_t Vl = (size_t)(sl.g1 - sl.g0), own = (size_t)(sl.e - sl.b), skip = (size_t)(sl.b - sl.g0);
-        auto download_rows = [&](void *dst, const void *src, size_t elem, size_t nrows) {
-            return copy_rows((char *)dst + (size_t)sl.b * elem, (size_t)V * elem, (const char *)src + skip * elem, Vl * elem, own * elem, nrows,
-                hipMemcpyDeviceToHost, sl.stream);
-        };
-        FVB_HIP_CHECK(download_rows(out->mvn, sl.dout.mvn, sizeof(double), (size_t)rows));
-        if (sl.dout.free_energy && out->free_energy)
-            FVB_HIP_CHECK(download_rows(out->free_energy, sl.dout.free_energy, sizeof(double), 1));
-        if (sl.dout.status && out->status)
-            FVB_HIP_CHECK(download_rows(out->status, sl.dout.status, sizeof(int32_t), 1));
-        if (sl.dout.iterations && out->iterations)
-            FVB_HIP_CHECK(download_rows(out->iterations, sl.dout.iterations, sizeof(int32_t), 1));
-        FVB_HIP_CHECK(hipStreamSynchronize(sl.stream));
+        const int rc = sl.staged.stage_out(out, sl.stream, nullptr, (size_t)(sl.b - sl.g0), (size_t)(sl.e - sl.b));
+        if (rc)
+            return rc;
     }
     return 0;
 }
