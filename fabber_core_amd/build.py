@@ -25,7 +25,7 @@ ARCH = "gfx950"
 
 HIP_SOURCES = ["vb_api.hip", "vb_lane_poly.hip", "vb_lane_linear.hip", "vb_lane_exp.hip", "vb_lane_wide.hip", "vb_lane_pattern_poly_2.hip", "vb_lane_pattern_poly_4.hip",
                "vb_lane_pattern_linear_2.hip", "vb_lane_pattern_linear_4.hip", "vb_lane_pattern_exp_2.hip", "vb_lane_pattern_exp_4.hip", "vb_lane_ar_poly.hip",
-               "vb_lane_ar_linear.hip", "vb_lane_ar_exp.hip", "vb_lane_arn_linear.hip", "vb_lane_arn_more.hip", "vb_spatial_api.hip", "vb_spatial_poly.hip",
+               "vb_lane_ar_linear.hip", "vb_lane_ar_exp.hip", "vb_lane_arn_linear.hip", "vb_lane_arn_more.hip", "vb_spatial_api.hip", "vb_spatial_multi.hip", "vb_spatial_poly.hip",
                "vb_spatial_linear.hip", "vb_spatial_exp.hip", "vb_spatial_host.hip", "vb_spatial_more.hip", "vb_spatial_wave.hip",
                "vb_spatial_nz_poly.hip", "vb_spatial_nz_linear.hip", "vb_spatial_nz_linear2.hip", "vb_spatial_nz_exp.hip", "vb_spatial_nz_host.hip",
                "vb_spatial_nz_arn.hip", "vb_spatial_nz_arn_linear2.hip", "vb_spatial_nz_arn_linear3.hip", "vb_spatial_nz_arn_linear4.hip", "vb_spatial_nz_arn_poly.hip",

@@ -41,12 +41,6 @@ int fail(int code, const std::string &msg)
     return code;
 }
 
-int noise_outputs(const fvb_config *cfg)
-{
-    // AR(1): (alphas, phi means), noisemodel_ar.cc:287-300
-    return cfg->noise == FVB_NOISE_WHITE ? cfg->n_phis : 2 + cfg->ar_cross_terms + cfg->n_phis;
-}
-
 int validate(const fvb_config *cfg, bool allow_spatial = false, bool allow_no_noise = false)
 {
     if (!cfg)

@@ -1,8 +1,8 @@
 /*
  * vb_host_stage.h - what the entry points that take HOST pointers share (vb_api.hip, vb_spatial_api.hip,
- * vb_hostmodel_api.hip, vb_nlls.hip): the error macro and the helpers of vb_api.hip, the device buffer type, the
- * parameter table on the device, a problem's inputs and outputs on the device (StagedProblem) and the loop of the
- * routes whose forward model is evaluated by the caller (HostModelLoop). No kernel includes this file.
+ * vb_spatial_multi.hip, vb_hostmodel_api.hip, vb_nlls.hip): the error macro and the helpers of vb_api.hip, the device
+ * buffer type, the parameter table on the device, a problem's inputs and outputs on the device (StagedProblem) and the
+ * loop of the routes whose forward model is evaluated by the caller (HostModelLoop). No kernel includes this file.
  */
 #pragma once
 
@@ -50,6 +50,13 @@ inline int count_unmasked(size_t T, const uint8_t *phi_index)
     for (size_t t = 0; t < T; t++)
         n += (phi_index[t] != 255);
     return n;
+}
+
+// entries of the noise block of the result MVN (WhiteParams / Ar1cParams::OutputAsMVN; AR(1): alphas and phi means,
+// noisemodel_ar.cc:287-300)
+inline int noise_outputs(const fvb_config *cfg)
+{
+    return cfg->noise == FVB_NOISE_WHITE ? cfg->n_phis : 2 + cfg->ar_cross_terms + cfg->n_phis;
 }
 
 // Device memory of ONE block of the pipelined host entry point: plain hipMalloc'd buffers that stay with the call's cached
