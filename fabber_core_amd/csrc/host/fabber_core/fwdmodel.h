@@ -62,6 +62,11 @@ struct DeviceModelSpec
     int iopt[4];
     double dopt[4];
     NEWMAT::Matrix design; // linear model: T x P
+    /** A body the model's own library registered with the engine (include/fabber_device_model.h): its registered
+     * name - `model` is then not looked at - and the constants the body reads (ModelArgs::consts). Used by voxelwise
+     * VB when the name is registered; everywhere else the model is evaluated on the host. */
+    std::string device_model;
+    std::vector<double> constants;
 };
 
 class FwdModel : public Loggable

@@ -129,7 +129,8 @@ void NLLSInferenceTechnique::DoCalculations(FabberRunData &rundata)
     DeviceModelSpec spec;
     // A model without a device body (any model library written for the reference), or any model when host-model is
     // set, is evaluated on the host - the minimiser's iterations stay on the GPU (fabber_nlls_run_hostmodel_host).
-    const bool device_model = m_model->GetDeviceModel(spec) && !rundata.GetBool("host-model");
+    // (a body registered by the model's library exists for voxelwise VB only: the host here)
+    const bool device_model = m_model->GetDeviceModel(spec) && spec.device_model.empty() && !rundata.GetBool("host-model");
     if (!device_model)
     {
         spec = DeviceModelSpec();

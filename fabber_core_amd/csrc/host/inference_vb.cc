@@ -109,6 +109,8 @@ struct Vb::EngineStorage
     vector<Parameter> params;
     vector<string> model_outputs;
     bool has_device_model;
+    bool library_device_model;     // ... and it is a body the model's library registered (FVB_MODEL_PLUGIN)
+    std::vector<double> constants; // its constants (fvb_config.model_consts)
     // more than FVB_MAX_PARAMS parameters: the per-parameter entries as a table (fvb_config.params_ext)
     vector<int32_t> wide_transform, wide_type;
     vector<double> wide_mean, wide_var, wide_prec, wide_post_mean, wide_post_var;
@@ -276,10 +278,31 @@ void Vb::BuildEngineConfig(FabberRunData &rundata, fvb_config &cfg)
     // when host-model is set, is evaluated on the host: 2P+1 Evaluate calls per voxel and
     // re-centre, everything else on the GPU (fabber_vb_run_hostmodel_host).
     st.has_device_model = m_model->GetDeviceModel(spec) && !rundata.GetBool("host-model");
+    // a body the model's library supplies counts when the library has registered it with the engine
+    st.library_device_model = st.has_device_model && !spec.device_model.empty();
+    if (st.library_device_model)
+    {
+        bool registered = false;
+        for (int i = 0; i < fabber_vb_device_model_count() && !registered; i++)
+        {
+            const char *name = fabber_vb_device_model_name(i);
+            registered = name && spec.device_model == name;
+        }
+        if (!registered || spec.device_model.size() >= sizeof(cfg.device_model))
+            st.has_device_model = st.library_device_model = false;
+    }
     if (!st.has_device_model)
     {
         spec = DeviceModelSpec();
         spec.model = FVB_MODEL_HOSTJAC;
+    }
+    if (st.library_device_model)
+    {
+        spec.model = FVB_MODEL_PLUGIN;
+        strncpy(cfg.device_model, spec.device_model.c_str(), sizeof(cfg.device_model) - 1);
+        st.constants = spec.constants;
+        cfg.model_consts = st.constants.empty() ? NULL : st.constants.data();
+        cfg.n_model_consts = (int32_t)st.constants.size();
     }
     cfg.model = spec.model;
     for (int i = 0; i < 4; i++)
@@ -794,7 +817,7 @@ void Vb::DoCalculations(FabberRunData &rundata)
             // no spatial kernels were built for this model with this many parameters: the model's own host code
             // does the re-centres instead (up to 32 parameters; more than 8 under white noise with one precision)
             LOG << "Vb::no device kernels for spatial VB with " << cfg.n_params << " parameters of this model" << endl;
-            m_store->has_device_model = false;
+            m_store->has_device_model = m_store->library_device_model = false;
             cfg.model = FVB_MODEL_HOSTJAC;
             cfg.design = NULL;
         }
@@ -826,6 +849,12 @@ void Vb::DoCalculations(FabberRunData &rundata)
     }
     else
     {
+        if (m_store->library_device_model)
+        {
+            // the kernels know no model's InitVoxelPosterior: the initial posterior comes from the model's host code
+            LOG << "Vb::the model runs on the device with the body '" << cfg.device_model << "' of its library" << endl;
+            BuildInitialMvn(rundata, cfg);
+        }
         LOG << "Vb::Voxelwise calculations on the MI355X engine, kernel " << fabber_vb_kernel_name(&cfg) << ", "
             << m_nvoxels << " voxels x " << cfg.n_times << " timepoints" << endl;
         if (devices_opt != "")
@@ -1040,7 +1069,8 @@ void InferenceTechnique::SaveEngineResults(FabberRunData &rundata, const fvb_con
 void Vb::SaveResults(FabberRunData &rundata) const
 {
     LOG << "Vb::Preparing to save results..." << endl;
-    SaveEngineResults(rundata, m_store->cfg, m_store->params, m_noise_params, m_noise->NumParams(), !m_store->has_device_model);
+    SaveEngineResults(rundata, m_store->cfg, m_store->params, m_noise_params, m_noise->NumParams(),
+        !m_store->has_device_model || m_store->library_device_model); // (model fit and residuals of a library's model: its host code)
     const int V = m_nvoxels;
     if (m_saveF && m_needF && !m_free_energy.empty())
     {

@@ -41,6 +41,41 @@ int fail(int code, const std::string &msg)
     return code;
 }
 
+// Device bodies that model libraries have registered (include/fabber_device_model.h). The descriptors are the
+// libraries' own static objects: they stay valid until the library unregisters them (the destructor of the object that
+// registered them does).
+struct DeviceModelRegistry
+{
+    std::mutex lock;
+    std::vector<const fvb_device_model *> models;
+};
+DeviceModelRegistry &device_models()
+{
+    static DeviceModelRegistry *r = new DeviceModelRegistry; // (never destroyed: libraries unregister from static destructors)
+    return *r;
+}
+// (the name as a configuration carries it: not necessarily terminated)
+std::string config_device_model(const fvb_config *cfg)
+{
+    return std::string(cfg->device_model, strnlen(cfg->device_model, sizeof(cfg->device_model)));
+}
+// launch (optional): the body's launcher, copied while the registry is locked - a descriptor may be unregistered by
+// another thread at any time; the library itself must stay loaded while a run that uses its body is under way
+bool find_device_model(const std::string &name, fvb_device_model_launch_fn *launch = nullptr)
+{
+    DeviceModelRegistry &r = device_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    for (const fvb_device_model *m : r.models)
+        if (name == m->name)
+        {
+            if (launch)
+                *launch = m->launch;
+            return true;
+        }
+    return false;
+}
+thread_local std::string g_kernel_name; // fabber_vb_kernel_name of a registered body: "wave<NAME>"
+
 int validate(const fvb_config *cfg, bool allow_spatial = false, bool allow_no_noise = false)
 {
     if (!cfg)
@@ -82,6 +117,16 @@ int validate(const fvb_config *cfg, bool allow_spatial = false, bool allow_no_no
         return fail(-11, "exp model: n_params != 2 * num-exps");
     if (cfg->model == FVB_MODEL_POLY && (cfg->n_params != cfg->model_iopt[0] + 1))
         return fail(-12, "poly model: n_params != degree + 1");
+    if (cfg->model == FVB_MODEL_PLUGIN)
+    {
+        const std::string name = config_device_model(cfg);
+        if (name.empty())
+            return fail(-16, "FVB_MODEL_PLUGIN needs the name of a registered device model (fvb_config.device_model)");
+        if (!find_device_model(name))
+            return fail(-16, "no device model '" + name + "' is registered (fabber_vb_register_device_model)");
+        if (cfg->n_model_consts < 0 || (cfg->n_model_consts > 0 && !cfg->model_consts))
+            return fail(-17, "device model '" + name + "': n_model_consts constants announced but model_consts is NULL");
+    }
     for (int k = 0; k < cfg->n_params; k++)
     {
         // (validate() sees the configuration as the caller built it: with device entry points the table itself is device
@@ -107,7 +152,8 @@ constexpr int WAVE_KERNEL_BELOW_VOXELS = 4096;
 
 LaneKernelInfo select_lane(const fvb_config *cfg)
 {
-    if (g_variant == 2 || (cfg->n_phis != 1 && cfg->noise == FVB_NOISE_WHITE && cfg->n_phis > 4))
+    // (a body from a model library exists as wave-per-voxel kernels only, whatever the voxel count and the variant asked for)
+    if (cfg->model == FVB_MODEL_PLUGIN || g_variant == 2 || (cfg->n_phis != 1 && cfg->noise == FVB_NOISE_WHITE && cfg->n_phis > 4))
         return LaneKernelInfo{ nullptr, 0, nullptr };
     if (cfg->noise == FVB_NOISE_AR1 && cfg->n_phis == 2) // two echoes: the two-pass kernel of vb_lane_arn_kernel.h
     {
@@ -540,10 +586,67 @@ void fabber_vb_set_residual_tolerance(double tol)
     g_residual_tol = tol;
 }
 
+int32_t fabber_vb_register_device_model(const fvb_device_model *model)
+{
+    if (!model || !model->name || !model->name[0] || !model->launch)
+        return fail(-70, "fabber_vb_register_device_model: descriptor, name or launcher is NULL");
+    const std::string name = model->name;
+    if (name.size() >= FVB_DEVICE_MODEL_NAME_MAX)
+        return fail(-70, "device model '" + name + "': the name is longer than " + std::to_string(FVB_DEVICE_MODEL_NAME_MAX - 1) + " characters");
+    if (model->abi_version != FVB_ABI_VERSION)
+        return fail(-71, "device model '" + name + "' was built for ABI version " + std::to_string(model->abi_version) + ", the engine is version "
+                + std::to_string(FVB_ABI_VERSION));
+    if (model->kernel_args_size != sizeof(KernelArgs) || model->wave_layout_size != sizeof(WaveLayout))
+        return fail(-72, "device model '" + name + "': struct size mismatch (KernelArgs " + std::to_string(model->kernel_args_size) + " against "
+                + std::to_string(sizeof(KernelArgs)) + " bytes, WaveLayout " + std::to_string(model->wave_layout_size) + " against "
+                + std::to_string(sizeof(WaveLayout)) + "): the library was compiled against other kernel headers");
+    DeviceModelRegistry &r = device_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    for (const fvb_device_model *m : r.models)
+        if (name == m->name)
+            return fail(-73, "a device model named '" + name + "' is already registered");
+    r.models.push_back(model);
+    return 0;
+}
+
+int32_t fabber_vb_unregister_device_model(const char *name)
+{
+    if (!name)
+        return fail(-70, "fabber_vb_unregister_device_model: name is NULL");
+    DeviceModelRegistry &r = device_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    for (size_t i = 0; i < r.models.size(); i++)
+        if (strcmp(r.models[i]->name, name) == 0)
+        {
+            r.models.erase(r.models.begin() + (long)i);
+            return 0;
+        }
+    return fail(-74, std::string("no device model '") + name + "' is registered");
+}
+
+int32_t fabber_vb_device_model_count(void)
+{
+    DeviceModelRegistry &r = device_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    return (int32_t)r.models.size();
+}
+
+const char *fabber_vb_device_model_name(int32_t i)
+{
+    DeviceModelRegistry &r = device_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->name : nullptr;
+}
+
 const char *fabber_vb_kernel_name(const fvb_config *cfg)
 {
     if (validate(cfg) != 0)
         return "invalid";
+    if (cfg->model == FVB_MODEL_PLUGIN)
+    {
+        g_kernel_name = "wave<" + config_device_model(cfg) + ">";
+        return g_kernel_name.c_str();
+    }
     LaneKernelInfo k = select_lane(cfg);
     if ((k.fn || k.fn_tiles_f32) && g_variant != 2)
         return k.name;
@@ -582,6 +685,8 @@ int run_device_as(const fvb_config *cfg, const void *data, const fvb_outputs *ou
         return fail(-21, "data is NULL");
     if (cfg->noise == FVB_NOISE_AR1 && n_unmasked != cfg->n_times)
         return fail(-15, "Masked time points are not supported for the AR noise model"); // noisemodel_ar.cc:351-355
+    if (cfg->model == FVB_MODEL_PLUGIN && !cfg->init_mvn) // (as for host-evaluated models: the kernels know no model's InitVoxelPosterior)
+        return fail(-52, "host-evaluated models need the initial posterior as init_mvn (the model's InitVoxelPosterior runs on the host)");
     api_keep_pool_memory();
     KernelArgs ka;
     ka.cfg = *cfg;
@@ -639,6 +744,16 @@ int run_device_as(const fvb_config *cfg, const void *data, const fvb_outputs *ou
             if (work && !slot)
                 FVB_HIP_CHECK(api_pool_free(work, stream));
         return 0;
+    }
+    if (cfg->model == FVB_MODEL_PLUGIN) // the kernels live in the library's code object: its launcher starts them
+    {
+        fvb_device_model_launch_fn launch = nullptr;
+        if (!find_device_model(config_device_model(cfg), &launch))
+            return fail(-16, "no device model '" + config_device_model(cfg) + "' is registered (fabber_vb_register_device_model)");
+        char msg[512];
+        msg[0] = 0;
+        rc = launch(&ka, (void *)stream, msg, (int32_t)sizeof(msg));
+        return rc ? fail(rc, msg) : 0;
     }
     return launch_wave_kernel(ka, stream, g_last_error);
 }
@@ -1037,7 +1152,9 @@ int32_t fabber_vb_run_host(const fvb_config *cfg, const void *data, const fvb_ou
     if (const char *e = getenv("FVB_HOST_BLOCK_VOXELS")) // (0 = one block, the round-2 behaviour)
         block = atoi(e) / 64 * 64;
     fvb_config choice = *cfg;
-    if (block > 0 && cfg->n_voxels >= 2 * block && (select_lane(&choice).fn || select_lane(&choice).fn_tiles_f32))
+    // (a library model's wave kernels take what they need from the block alone, like the lane kernels: piped as well)
+    if (block > 0 && cfg->n_voxels >= 2 * block
+        && (select_lane(&choice).fn || select_lane(&choice).fn_tiles_f32 || cfg->model == FVB_MODEL_PLUGIN))
         return run_host_pipelined(cfg, data, out, device, block);
     return run_host_block(cfg, data, out, device, 0, cfg->n_voxels, nullptr, cfg->n_voxels);
 }

@@ -135,6 +135,7 @@ __global__ __launch_bounds__(64) void vb_wave_step_kernel(const HmArgs ha)
     ma.iopt0 = 0;
     ma.dopt0 = 0;
     ma.design = nullptr;
+    ma.model = FVB_MODEL_HOSTJAC;
 
     // ---- the voxel's series and noise pattern (re-staged every step; T floats) ----
     FVB_WAVE_FOR(t, T)

@@ -46,6 +46,7 @@ __global__ __launch_bounds__(64) void vb_wave_ar_step_kernel(const HmArgs ha)
     ma.iopt0 = 0;
     ma.dopt0 = 0;
     ma.design = nullptr;
+    ma.model = FVB_MODEL_HOSTJAC;
 
     FVB_WAVE_FOR(t, T)
     {

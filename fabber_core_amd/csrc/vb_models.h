@@ -48,6 +48,12 @@ struct ModelArgs
     int32_t lin_T;
     // the kernel's copy of the table of exp_acc (vb_math.h) in LDS, or NULL (kernels built with recentre<..., ACC>)
     const double *exp_table;
+    // a device body from a model library (FVB_MODEL_PLUGIN, include/fabber_device_model.h): the model's constants
+    // (fvb_config.model_consts) - device memory, wave-uniform, read-only; not staged in LDS
+    const double *consts;
+    int32_t n_consts;
+    // the wave-per-voxel kernels' built-in evaluator (vb_wave_kernel.h): fvb_config.model, for eval_model_runtime
+    int32_t model;
 };
 
 // A "sweep" produces, for t = 0, 1, 2, ... in order, the 2P + 1 predictions the central

@@ -413,6 +413,7 @@ __global__ __launch_bounds__(64) void nlls_wave_kernel(const NllsArgs na, const 
     ma.iopt0 = ka.cfg.model_iopt[0];
     ma.dopt0 = ka.cfg.model_dopt[0];
     ma.design = ka.cfg.design;
+    ma.model = ka.cfg.model;
 
     nlls_wave_stage(ka, cx);
     FVB_WAVE_FOR(i, L.P)
@@ -461,6 +462,7 @@ __global__ __launch_bounds__(64) void nlls_wave_step_kernel(const NllsHmArgs ha)
     ma.iopt0 = 0;
     ma.dopt0 = 0;
     ma.design = nullptr;
+    ma.model = FVB_MODEL_HOSTJAC;
 
     nlls_wave_stage(ka, cx);
     NllsHmScalars sc = ha.scalars[v];

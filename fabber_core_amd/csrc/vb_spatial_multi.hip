@@ -548,6 +548,8 @@ static int32_t spatial_multi_validate(const fvb_config *cfg, const fvb_spatial *
         return api_fail(-44, spatial_noise_refusal);
     if (cfg->model == FVB_MODEL_HOSTJAC)
         return api_fail(-56, "a model evaluated on the host runs spatial VB on one device (fabber_vb_run_spatial_hostmodel_host)");
+    if (cfg->model == FVB_MODEL_PLUGIN) // (a library's body exists as voxelwise wave kernels only: as the one-device entry point answers)
+        return api_fail(-40, "no spatial kernel instantiation for this model / parameter count / noise model");
     if (!out || !out->mvn)
         return api_fail(-20, "outputs.mvn is required");
     return 0;

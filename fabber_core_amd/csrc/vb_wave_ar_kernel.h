@@ -687,8 +687,8 @@ __device__ __forceinline__ void ar_write_outputs(const KernelArgs &ka, WaveCtx &
     }
 }
 
-template <int NPHI, int NA, bool NEEDF>
-__global__ __launch_bounds__(64) void vb_wave_ar_kernel(const KernelArgs ka, const WaveLayout L)
+template <class Eval, int NPHI, int NA, bool NEEDF>
+__device__ __forceinline__ void wave_ar_kernel_body(const KernelArgs &ka, const WaveLayout &L)
 {
     extern __shared__ double wave_lds[];
     WaveCtx cx;
@@ -703,10 +703,7 @@ __global__ __launch_bounds__(64) void vb_wave_ar_kernel(const KernelArgs ka, con
     const size_t V = cx.V;
     double *sh = cx.sh;
 
-    ModelArgs ma;
-    ma.iopt0 = ka.cfg.model_iopt[0];
-    ma.dopt0 = ka.cfg.model_dopt[0];
-    ma.design = ka.cfg.design;
+    const ModelArgs ma = wave_model_args(ka);
 
     FVB_WAVE_FOR(t, T)
     {
@@ -820,7 +817,7 @@ __global__ __launch_bounds__(64) void vb_wave_ar_kernel(const KernelArgs ka, con
     const bool use_save = ka.cfg.convergence == FVB_CONV_FREDUCE || ka.cfg.convergence == FVB_CONV_TRIALMODE
         || ka.cfg.convergence == FVB_CONV_LM;
 
-    int status = wave_recentre(ka, ma, cx, false); // inference_vb.cc:235 and :443
+    int status = wave_recentre<Eval>(ka, ma, cx, false); // inference_vb.cc:235 and :443
     if (status != FVB_OK)
         setup_failed = true;
     // Precalculate (noisemodel_ar.cc:749-769)
@@ -891,7 +888,7 @@ __global__ __launch_bounds__(64) void vb_wave_ar_kernel(const KernelArgs ka, con
             ar_update_phi<NPHI, NA>(ka, cx, st);
             if (NEEDF)
                 FVB_AR_EVAL_F()
-            status = wave_recentre(ka, ma, cx, false);
+            status = wave_recentre<Eval>(ka, ma, cx, false);
             if (status != FVB_OK)
                 break;
             if (NEEDF)
@@ -914,7 +911,7 @@ __global__ __launch_bounds__(64) void vb_wave_ar_kernel(const KernelArgs ka, con
             {
                 wave_restore_state(cx);
                 st = st_saved;
-                status = wave_recentre(ka, ma, cx, false);
+                status = wave_recentre<Eval>(ka, ma, cx, false);
                 if (status == FVB_OK && NEEDF)
                 {
                     do
@@ -928,6 +925,19 @@ __global__ __launch_bounds__(64) void vb_wave_ar_kernel(const KernelArgs ka, con
     }
 
     ar_write_outputs<NPHI, NA>(ka, cx, st, status, setup_failed, F, it, hist_len);
+}
+
+// the engine's kernel (built-in models) and the same loop around a model library's evaluator, as vb_wave_kernel
+template <int NPHI, int NA, bool NEEDF>
+__global__ __launch_bounds__(64) void vb_wave_ar_kernel(const KernelArgs ka, const WaveLayout L)
+{
+    wave_ar_kernel_body<BuiltinEval, NPHI, NA, NEEDF>(ka, L);
+}
+
+template <class Eval, int NPHI, int NA, bool NEEDF>
+__global__ __launch_bounds__(64) void vb_wave_ar_model_kernel(const KernelArgs ka, const WaveLayout L)
+{
+    wave_ar_kernel_body<Eval, NPHI, NA, NEEDF>(ka, L);
 }
 
 #endif // __HIPCC__

@@ -3,7 +3,8 @@
  *
  * The general form of the hot path: any parameter count up to FVB_MAX_PARAMS, any white-noise
  * pattern (several noise precisions phi_i, masked timepoints), any built-in model through
- * eval_model_runtime. It is also the mapping that keeps the chip busy when there are few voxels
+ * eval_model_runtime - or the body a model library supplies (the kernels are templates on an evaluator,
+ * include/fabber_device_model.h instantiates them in the library's own code object). It is also the mapping that keeps the chip busy when there are few voxels
  * (a 64 x 64 slice is 64 waves for the lane kernel, 4096 here).
  *
  *   - the 64 lanes split the TIMEPOINTS: lane l owns t = l, l + 64, ... for the 2P + 1 model
@@ -211,9 +212,34 @@ __device__ __forceinline__ bool wave_ensure_prec(WaveCtx &cx)
     return ok;
 }
 
+// What evaluates the model in wave_recentre: a stateless struct with
+//     static __device__ double eval(const ModelArgs &a, int P, int t, const double *model_space_params)
+// The built-in one is the engine's own models; a model library provides its own (include/fabber_device_model.h).
+struct BuiltinEval
+{
+    static __device__ __forceinline__ double eval(const ModelArgs &a, int P, int t, const double *p)
+    {
+        return eval_model_runtime(a.model, a, P, t, p);
+    }
+};
+
+// the model's side of the kernel arguments, as every wave-per-voxel kernel hands it to its evaluator
+__device__ __forceinline__ ModelArgs wave_model_args(const KernelArgs &ka)
+{
+    ModelArgs ma;
+    ma.iopt0 = ka.cfg.model_iopt[0];
+    ma.dopt0 = ka.cfg.model_dopt[0];
+    ma.design = ka.cfg.design;
+    ma.consts = ka.cfg.model_consts;
+    ma.n_consts = ka.cfg.n_model_consts;
+    ma.model = ka.cfg.model;
+    return ma;
+}
+
 // LinearizedFwdModel::ReCentre about the current means (fwdmodel_linear.cc:126-182) followed by
 // the per-phi moments A_i = J'Q_iJ, u_i = J'Q_i r, s_i = r'Q_i r with r = y - g(ml).
 // moments = false: only g, J and r (the AR kernel forms its own contractions)
+template <class Eval = BuiltinEval>
 __device__ __forceinline__ int wave_recentre(const KernelArgs &ka, const ModelArgs &ma, WaveCtx &cx, bool moments = true)
 {
     const WaveLayout &L = cx.L;
@@ -266,14 +292,14 @@ __device__ __forceinline__ int wave_recentre(const KernelArgs &ka, const ModelAr
     wave_sync();
     FVB_WAVE_FOR(t, T)
     {
-        const double g = eval_model_runtime(ka.cfg.model, ma, P, t, sh + L.pv);
+        const double g = Eval::eval(ma, P, t, sh + L.pv);
         sh[L.gl + t] = g;
         bad_offset |= !is_finite(g);
         for (int i = 0; i < P; i++)
         {
             FVB_MODEL_FP
-            const double f2 = eval_model_runtime(ka.cfg.model, ma, P, t, sh + L.pv + (1 + 2 * i) * P);
-            const double f3 = eval_model_runtime(ka.cfg.model, ma, P, t, sh + L.pv + (2 + 2 * i) * P);
+            const double f2 = Eval::eval(ma, P, t, sh + L.pv + (1 + 2 * i) * P);
+            const double f3 = Eval::eval(ma, P, t, sh + L.pv + (2 + 2 * i) * P);
             const double Jti = (f2 - f3) * sh[L.rden + i];
             sh[L.J + t * Ps + i] = Jti;
             bad_jac |= !is_finite(Jti);
@@ -627,8 +653,8 @@ __device__ __forceinline__ void wave_restore_state(WaveCtx &cx)
     wave_sync();
 }
 
-template <bool NEEDF>
-__global__ __launch_bounds__(64) void vb_wave_kernel(const KernelArgs ka, const WaveLayout L)
+template <class Eval, bool NEEDF>
+__device__ __forceinline__ void wave_kernel_body(const KernelArgs &ka, const WaveLayout &L)
 {
     extern __shared__ double wave_lds[];
     WaveCtx cx;
@@ -643,10 +669,7 @@ __global__ __launch_bounds__(64) void vb_wave_kernel(const KernelArgs ka, const 
     const size_t V = cx.V;
     double *sh = cx.sh;
 
-    ModelArgs ma;
-    ma.iopt0 = ka.cfg.model_iopt[0];
-    ma.dopt0 = ka.cfg.model_dopt[0];
-    ma.design = ka.cfg.design;
+    const ModelArgs ma = wave_model_args(ka);
 
     // ---- stage the voxel's time series and the noise pattern ----
     FVB_WAVE_FOR(t, T)
@@ -730,7 +753,7 @@ __global__ __launch_bounds__(64) void vb_wave_kernel(const KernelArgs ka, const 
     const bool use_save = ka.cfg.convergence == FVB_CONV_FREDUCE || ka.cfg.convergence == FVB_CONV_TRIALMODE
         || ka.cfg.convergence == FVB_CONV_LM;
 
-    int status = wave_recentre(ka, ma, cx); // inference_vb.cc:235 and :443 share one pass
+    int status = wave_recentre<Eval>(ka, ma, cx); // inference_vb.cc:235 and :443 share one pass
     if (status != FVB_OK)
         setup_failed = true;
 
@@ -788,7 +811,7 @@ __global__ __launch_bounds__(64) void vb_wave_kernel(const KernelArgs ka, const 
             wave_update_noise(ka, cx); // :479
             if (NEEDF) // "phi" :485
                 FVB_WAVE_EVAL_F()
-            status = wave_recentre(ka, ma, cx); // :490
+            status = wave_recentre<Eval>(ka, ma, cx); // :490
             if (status != FVB_OK)
                 break;
             if (NEEDF) // "lin" :495
@@ -810,7 +833,7 @@ __global__ __launch_bounds__(64) void vb_wave_kernel(const KernelArgs ka, const 
             if (use_save && conv_need_revert(conv)) // :516-525
             {
                 wave_restore_state(cx);
-                status = wave_recentre(ka, ma, cx);
+                status = wave_recentre<Eval>(ka, ma, cx);
                 if (status == FVB_OK && NEEDF)
                 {
                     do
@@ -876,6 +899,20 @@ __global__ __launch_bounds__(64) void vb_wave_kernel(const KernelArgs ka, const 
         if (ka.out.iterations)
             ka.out.iterations[v] = it;
     }
+}
+
+// the engine's kernel (built-in models) ...
+template <bool NEEDF>
+__global__ __launch_bounds__(64) void vb_wave_kernel(const KernelArgs ka, const WaveLayout L)
+{
+    wave_kernel_body<BuiltinEval, NEEDF>(ka, L);
+}
+
+// ... and the same loop around a model library's evaluator
+template <class Eval, bool NEEDF>
+__global__ __launch_bounds__(64) void vb_wave_model_kernel(const KernelArgs ka, const WaveLayout L)
+{
+    wave_kernel_body<Eval, NEEDF>(ka, L);
 }
 
 #endif // __HIPCC__

@@ -72,6 +72,13 @@ def lib():
         L.fabber_nlls_run_device.argtypes = [cfgp, C.POINTER(vbabi.FvbNlls), C.c_void_p, outp, C.c_void_p, C.c_int32]
         L.fabber_nlls_defaults.restype = None
         L.fabber_nlls_defaults.argtypes = [C.POINTER(vbabi.FvbNlls)]
+        L.fabber_vb_register_device_model.restype = C.c_int32
+        L.fabber_vb_register_device_model.argtypes = [C.POINTER(vbabi.FvbDeviceModel)]
+        L.fabber_vb_unregister_device_model.restype = C.c_int32
+        L.fabber_vb_unregister_device_model.argtypes = [C.c_char_p]
+        L.fabber_vb_device_model_count.restype = C.c_int32
+        L.fabber_vb_device_model_name.restype = C.c_char_p
+        L.fabber_vb_device_model_name.argtypes = [C.c_int32]
         if L.fabber_vb_abi_version() != vbabi.FVB_ABI_VERSION:
             raise HipEngineError("libfabber_vb_hip.so ABI version mismatch: rebuild")
         _LIB = L
@@ -85,6 +92,38 @@ def _check(rc):
 
 def device_count():
     return lib().fabber_vb_device_count()
+
+
+_MODEL_LIBRARIES = {}
+
+
+def load_model_library(path):
+    """Open a model library that carries device bodies (include/fabber_device_model.h): its static objects register
+    them with the engine, after which build_config(MODEL_PLUGIN, device_model=name) can name them. The engine is
+    loaded first and both are opened with RTLD_GLOBAL, so that the library finds the engine's registry. Returns the
+    ctypes handle; a library is opened once per process."""
+    path = os.path.abspath(path)
+    if path not in _MODEL_LIBRARIES:
+        lib()
+        C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)  # (the same handle, its symbols now visible to what is opened next)
+        _MODEL_LIBRARIES[path] = C.CDLL(path, mode=C.RTLD_GLOBAL)
+    return _MODEL_LIBRARIES[path]
+
+
+def device_models():
+    """Names of the device bodies registered with the engine."""
+    L = lib()
+    return [L.fabber_vb_device_model_name(i).decode() for i in range(L.fabber_vb_device_model_count())]
+
+
+def register_device_model(descriptor):
+    """fabber_vb_register_device_model with a vbabi.FvbDeviceModel (the caller keeps it alive); raises with the engine's
+    message when the registration is refused."""
+    _check(lib().fabber_vb_register_device_model(C.byref(descriptor)))
+
+
+def unregister_device_model(name):
+    _check(lib().fabber_vb_unregister_device_model(name.encode()))
 
 
 def kernel_name(holder):

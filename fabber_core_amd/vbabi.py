@@ -15,9 +15,10 @@ import numpy as np
 FVB_MAX_PARAMS = 32
 FVB_MAX_PHIS = 8
 FVB_MAX_ALPHAS = 4
-FVB_ABI_VERSION = 9
+FVB_ABI_VERSION = 10
+FVB_DEVICE_MODEL_NAME_MAX = 48
 
-MODEL_POLY, MODEL_LINEAR, MODEL_EXP, MODEL_HOSTJAC = 0, 1, 2, 100
+MODEL_POLY, MODEL_LINEAR, MODEL_EXP, MODEL_HOSTJAC, MODEL_PLUGIN = 0, 1, 2, 100, 101
 TRANSFORM_IDENTITY, TRANSFORM_LOG, TRANSFORM_SOFTPLUS, TRANSFORM_FRACTIONAL, TRANSFORM_ABS = range(5)
 TRANSFORM_CODES = {"I": 0, "L": 1, "S": 2, "F": 3, "A": 4}
 PRIOR_NORMAL, PRIOR_IMAGE, PRIOR_ARD, PRIOR_SPATIAL_M, PRIOR_SPATIAL_m, PRIOR_SPATIAL_P, PRIOR_SPATIAL_p = range(7)
@@ -77,7 +78,17 @@ class FvbConfig(C.Structure):
         ("ar_alpha_post_mean", C.c_double * FVB_MAX_ALPHAS),
         ("ar_alpha_post_cov", (C.c_double * FVB_MAX_ALPHAS) * FVB_MAX_ALPHAS),
         ("params_ext", C.c_void_p),
+        ("device_model", C.c_char * FVB_DEVICE_MODEL_NAME_MAX),
+        ("model_consts", C.c_void_p),
+        ("n_model_consts", C.c_int32),
     ]
+
+
+class FvbDeviceModel(C.Structure):
+    """fvb_device_model: what a model library registers for a device body (include/fabber_device_model.h)"""
+    LAUNCH_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32)
+    _fields_ = [("name", C.c_char_p), ("abi_version", C.c_int32), ("kernel_args_size", C.c_uint32), ("wave_layout_size", C.c_uint32),
+                ("launch", LAUNCH_FN)]
 
 
 class FvbOutputs(C.Structure):
@@ -208,8 +219,13 @@ def build_config(model, n_voxels, n_times, *, degree=None, design=None, num_exps
                  need_f=None, f_history_rows=0, noise_pattern="1", masked_timepoints=(),
                  prior_noise_stddev=-1.0, locked_noise_stdev=-1.0, param_overrides=None,
                  image_priors=None, init_mvn=None, noise=NOISE_WHITE, num_echoes=1, ar_cross_terms="none",
-                 ar_alpha_prior=None, ar_alpha_post=None):
+                 ar_alpha_prior=None, ar_alpha_post=None, device_model=None, constants=None, params=None):
     """Resolve options into an fvb_config whose pointer members are HOST numpy arrays.
+
+    MODEL_PLUGIN (a device body registered by a model library, hiplib.load_model_library): device_model = its
+    registered name, constants = what the body reads as ModelArgs::consts, params = the model's parameter defaults
+    (as model_parameter_defaults returns them); num_exps and dt travel as model_iopt[0] / model_dopt[0]. Such a
+    model needs init_mvn.
 
     param_overrides: {name: dict(type=, mean=, prec=, transform=)} == PSP_byname options
     (fwdmodel.cc:238-266). image_priors: {name: float64 array [n_voxels]}.
@@ -234,6 +250,21 @@ def build_config(model, n_voxels, n_times, *, degree=None, design=None, num_exps
         cfg.model_iopt[0] = int(num_exps)
         cfg.model_dopt[0] = float(dt)
         params = model_parameter_defaults(model, num_exps=num_exps)
+    elif model == MODEL_PLUGIN:
+        name = (device_model or "").encode()
+        if len(name) >= FVB_DEVICE_MODEL_NAME_MAX:
+            raise ValueError("device model name too long: %r" % device_model)
+        cfg.device_model = name
+        cfg.model_iopt[0] = int(num_exps)
+        cfg.model_dopt[0] = float(dt)
+        if constants is not None:
+            constants = np.ascontiguousarray(constants, dtype=np.float64).ravel()
+            keep["constants"] = constants
+            cfg.model_consts = constants.ctypes.data
+            cfg.n_model_consts = constants.size
+        if not params:
+            raise ValueError("MODEL_PLUGIN: params (the model's parameter defaults) are required")
+        params = [dict(p) for p in params]
     else:
         raise ValueError(model)
     P = len(params)

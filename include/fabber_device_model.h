@@ -1,0 +1,106 @@
+/*
+ * fabber_device_model.h - give a forward model of a model library a DEVICE body.
+ *
+ * A model library is loaded at run time and its models are evaluated on the host unless the library also supplies
+ * a body the engine's kernels can call. Device functions cannot be called across code objects, so the library does
+ * not hand over a function: it compiles the engine's wave-per-voxel kernels (one wavefront per voxel, any parameter
+ * count, white noise with any pattern and AR(1) noise) around its own evaluator into its OWN code object, and registers
+ * a host launcher for them. This header is HIP C++: compile the file that uses it with
+ *
+ *     hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-fast-math -I <this directory> ...
+ *
+ * The body is a stateless struct:
+ *
+ *     struct InvRec
+ *     {
+ *         // prediction at timepoint index t (0-based) for MODEL-space parameters p[0 .. P-1], i.e. what
+ *         // FwdModel::EvaluateModel receives after the parameter transforms
+ *         static __device__ double eval(const fvb::ModelArgs &a, int P, int t, const double *p)
+ *         {
+ *             FVB_MODEL_FP // the floating-point contraction setting of the built-in bodies
+ *             if (t >= a.n_consts) // the engine does not know how many constants a body needs: the body never reads
+ *                 return __builtin_nan(""); // past the block (a non-finite prediction stops the voxel with its status)
+ *             return p[0] * (1.0 - 2.0 * p[2] * exp(-a.consts[t] / p[1]));
+ *         }
+ *     };
+ *     FABBER_DEVICE_MODEL("invrec", InvRec)
+ *
+ * a.consts / a.n_consts are the model's constants (a list of inversion times, a dose, a TR): read-only device memory,
+ * the same for every voxel, filled from DeviceModelSpec::constants (fvb_config.model_consts). The expression must be
+ * the one the model's host EvaluateModel computes - the host code still provides the initial posterior, the result
+ * images, and the whole fit wherever the device body is not used (spatial VB, method=nlls, the host-model option).
+ *
+ * The macro, at namespace scope, once per model:
+ *   - instantiates the white-noise kernel (with and without the free energy) and the four AR(1) kernels for the body;
+ *   - defines the launcher (LDS attribute above 64 KB, one workgroup per voxel, the engine's error texts);
+ *   - registers { name, FVB_ABI_VERSION, sizeof(KernelArgs), sizeof(WaveLayout), launcher } with the engine from a
+ *     static object whose destructor unregisters it. A library built against other headers than the engine is refused
+ *     at registration (fabber_vb_last_error says why) and its models run on the host.
+ *
+ * Name the body struct uniquely or put it in an anonymous namespace: the kernels and the launcher are template
+ * instantiations on it, and two libraries in one process whose bodies share a global name would share those symbols
+ * (the first loaded wins). Link the library against the engine library the process uses - another copy of it has
+ * another registry - and keep it loaded while a run that uses the body is under way.
+ *
+ * The host side of the model announces the body through FwdModel::GetDeviceModel: spec.device_model = "invrec",
+ * spec.constants = the constants.
+ */
+#ifndef FABBER_DEVICE_MODEL_H
+#define FABBER_DEVICE_MODEL_H
+
+#include "fabber_vb.h"
+#include "../fabber_core_amd/csrc/vb_wave_launch.h"
+
+#include <cstdio>
+#include <cstring>
+#include <string>
+
+namespace fvb
+{
+template <class Eval>
+int32_t device_model_launch(const void *kernel_args, void *stream, char *err, int32_t err_len)
+{
+    static const WaveKernelSet set = wave_model_kernels<Eval>();
+    std::string msg;
+    const int rc = launch_wave_set(set, *static_cast<const KernelArgs *>(kernel_args), static_cast<hipStream_t>(stream), msg);
+    if (rc && err && err_len > 0)
+    {
+        strncpy(err, msg.c_str(), (size_t)err_len - 1);
+        err[err_len - 1] = 0;
+    }
+    return rc;
+}
+
+// registers in its constructor, unregisters in its destructor (the library's static object)
+struct DeviceModelRegistration
+{
+    fvb_device_model descriptor;
+    bool registered;
+    DeviceModelRegistration(const char *name, fvb_device_model_launch_fn launch)
+    {
+        descriptor.name = name;
+        descriptor.abi_version = FVB_ABI_VERSION;
+        descriptor.kernel_args_size = (uint32_t)sizeof(KernelArgs);
+        descriptor.wave_layout_size = (uint32_t)sizeof(WaveLayout);
+        descriptor.launch = launch;
+        registered = fabber_vb_register_device_model(&descriptor) == 0;
+        if (!registered)
+            fprintf(stderr, "fabber: device model '%s' not registered (%s): the model runs on the host\n", name, fabber_vb_last_error());
+    }
+    ~DeviceModelRegistration()
+    {
+        if (registered)
+            (void)fabber_vb_unregister_device_model(descriptor.name);
+    }
+    DeviceModelRegistration(const DeviceModelRegistration &) = delete;
+    DeviceModelRegistration &operator=(const DeviceModelRegistration &) = delete;
+};
+} // namespace fvb
+
+#define FABBER_DEVICE_MODEL_CAT2(a, b) a##b
+#define FABBER_DEVICE_MODEL_CAT(a, b) FABBER_DEVICE_MODEL_CAT2(a, b)
+#define FABBER_DEVICE_MODEL(NAME, EVAL)                                                                      \
+    static fvb::DeviceModelRegistration FABBER_DEVICE_MODEL_CAT(fabber_device_model_registration_, __LINE__)( \
+        NAME, &fvb::device_model_launch<EVAL>);
+
+#endif /* FABBER_DEVICE_MODEL_H */

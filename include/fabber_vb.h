@@ -46,17 +46,21 @@ extern "C" {
 #define FVB_MAX_PARAMS_EXT 128 /* with fvb_config.params_ext (the wave-per-voxel kernels; what their LDS holds decides) */
 #define FVB_MAX_PHIS 8
 #define FVB_MAX_ALPHAS 4 /* AR(1) coefficients: 2 + ar_cross_terms (noisemodel_ar.cc:360-377) */
-#define FVB_ABI_VERSION 9
+#define FVB_ABI_VERSION 10
+#define FVB_DEVICE_MODEL_NAME_MAX 48 /* bytes of a registered device-model name, the terminator included */
 
 /* Forward models with a device body (fwdmodel_poly.cc:62, fwdmodel_linear.cc:92,
  * examples/fwdmodel_exp.cc:65). FVB_MODEL_HOSTJAC = model only exists as a host plugin;
- * its offset / Jacobian are supplied per re-centre by the host (fabber_vb_run_hostmodel_host). */
+ * its offset / Jacobian are supplied per re-centre by the host (fabber_vb_run_hostmodel_host).
+ * FVB_MODEL_PLUGIN = the device body lives in a model library that registered it under
+ * fvb_config.device_model (fabber_vb_register_device_model; include/fabber_device_model.h). */
 enum fvb_model
 {
     FVB_MODEL_POLY = 0,
     FVB_MODEL_LINEAR = 1,
     FVB_MODEL_EXP = 2,
-    FVB_MODEL_HOSTJAC = 100
+    FVB_MODEL_HOSTJAC = 100,
+    FVB_MODEL_PLUGIN = 101
 };
 
 /* transforms.h:19-23 */
@@ -192,6 +196,12 @@ typedef struct fvb_config
     /* ---- more than FVB_MAX_PARAMS parameters ---- */
     const fvb_param_table *params_ext; /* NULL: the fixed arrays above; else n_params may exceed FVB_MAX_PARAMS and every
                                           per-parameter entry is read from this table (the fixed arrays are ignored) */
+
+    /* ---- FVB_MODEL_PLUGIN: a device body registered by a model library ---- */
+    char device_model[FVB_DEVICE_MODEL_NAME_MAX]; /* the registered name, NUL-terminated */
+    const double *model_consts; /* [n_model_consts] constants of the model (a list of inversion times, a dose, a TR ...):
+                                   what the body finds in ModelArgs::consts. Same memory space as data; may be NULL. */
+    int32_t n_model_consts;
 } fvb_config;
 
 /* the per-parameter entries wherever they are (host code) */
@@ -230,7 +240,31 @@ int32_t fabber_vb_abi_version(void);
 int32_t fabber_vb_device_count(void);
 const char *fabber_vb_last_error(void);
 
-/* Which kernel a configuration would dispatch to ("lane<exp,4>" / "wave" / ...). */
+/*
+ * Device bodies supplied by model libraries. A library compiles the wave-per-voxel kernels for its own evaluator
+ * into its own code object (FABBER_DEVICE_MODEL in include/fabber_device_model.h) and registers a descriptor: the
+ * engine never sees a device function of the library, it calls the library's host launcher. `launch` receives the
+ * engine's kernel arguments (fvb::KernelArgs, sizeof = kernel_args_size; the launcher derives the LDS layout,
+ * sizeof(fvb::WaveLayout) = wave_layout_size, from them), launches asynchronously on `stream` (a hipStream_t) and returns
+ * 0 or a negative code with its message in err. Registration is refused (negative code, message in
+ * fabber_vb_last_error) for a duplicate name, another ABI version or other struct sizes. The descriptor and its
+ * name must stay valid until fabber_vb_unregister_device_model.
+ */
+typedef int32_t (*fvb_device_model_launch_fn)(const void *kernel_args, void *stream, char *err, int32_t err_len);
+typedef struct fvb_device_model
+{
+    const char *name;
+    int32_t abi_version;       /* FVB_ABI_VERSION the library was compiled against */
+    uint32_t kernel_args_size; /* sizeof(fvb::KernelArgs) */
+    uint32_t wave_layout_size; /* sizeof(fvb::WaveLayout) */
+    fvb_device_model_launch_fn launch;
+} fvb_device_model;
+int32_t fabber_vb_register_device_model(const fvb_device_model *model);
+int32_t fabber_vb_unregister_device_model(const char *name);
+int32_t fabber_vb_device_model_count(void);
+const char *fabber_vb_device_model_name(int32_t i); /* NULL when i is out of range */
+
+/* Which kernel a configuration would dispatch to ("lane<exp,4>" / "wave" / "wave<NAME>" for a registered body ...). */
 const char *fabber_vb_kernel_name(const fvb_config *cfg);
 
 /*
