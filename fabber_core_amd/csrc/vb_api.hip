@@ -5,7 +5,7 @@
  * There is no CPU fallback: if no HIP device is present or a launch fails the call returns a
  * negative code and fabber_vb_last_error() says why.
  */
-#include "vb_dispatch.h"
+#include "vb_lane_launch.h"
 #include "vb_host_stage.h"
 #include "vb_wave_kernel.h"
 
@@ -74,7 +74,33 @@ bool find_device_model(const std::string &name, fvb_device_model_launch_fn *laun
         }
     return false;
 }
-thread_local std::string g_kernel_name; // fabber_vb_kernel_name of a registered body: "wave<NAME>"
+// The lane-per-voxel kernels of such bodies (include/fabber_device_lane_model.h), by (name, parameter count): a
+// registry of its own, looked into only for a name the one above holds.
+struct DeviceLaneModelRegistry
+{
+    std::mutex lock;
+    std::vector<const fvb_device_lane_model *> models;
+};
+DeviceLaneModelRegistry &device_lane_models()
+{
+    static DeviceLaneModelRegistry *r = new DeviceLaneModelRegistry; // (never destroyed, as above)
+    return *r;
+}
+// (copies what a run needs while the registry is locked, as find_device_model does)
+bool find_device_lane_model(const std::string &name, int n_params, fvb_device_lane_launch_fn *launch, int *save_rows)
+{
+    DeviceLaneModelRegistry &r = device_lane_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    for (const fvb_device_lane_model *m : r.models)
+        if (m->n_params == n_params && name == m->name)
+        {
+            *launch = m->launch;
+            *save_rows = m->save_rows;
+            return true;
+        }
+    return false;
+}
+thread_local std::string g_kernel_name; // fabber_vb_kernel_name of a registered body: "wave<NAME>", "lane<NAME,P>"
 
 int validate(const fvb_config *cfg, bool allow_spatial = false, bool allow_no_noise = false)
 {
@@ -150,10 +176,32 @@ int validate(const fvb_config *cfg, bool allow_spatial = false, bool allow_no_no
 // C2 fit (lane 0.12 ms flat, wave 0.04 us per voxel).
 constexpr int WAVE_KERNEL_BELOW_VOXELS = 4096;
 
-LaneKernelInfo select_lane(const fvb_config *cfg)
+// The lane kernels a configuration runs on: the engine's own (k) or, for a body from a model library, the ones its
+// library compiled (launch: the library's launcher; of k only save_rows is set). Neither: the wave-per-voxel kernels.
+struct LaneRoute
 {
-    // (a body from a model library exists as wave-per-voxel kernels only, whatever the voxel count and the variant asked for)
-    if (cfg->model == FVB_MODEL_PLUGIN || g_variant == 2 || (cfg->n_phis != 1 && cfg->noise == FVB_NOISE_WHITE && cfg->n_phis > 4))
+    LaneKernelInfo k{ nullptr, 0, nullptr };
+    fvb_device_lane_launch_fn launch = nullptr;
+    bool any() const
+    {
+        return k.fn || k.fn_tiles_f32 || launch;
+    }
+};
+
+// the size rule of the white-noise lane kernels: false = the wave-per-voxel kernel finishes first
+bool lane_worth_it(const fvb_config *cfg, double evaluations)
+{
+    // ... for models whose re-linearisation is long enough to be worth sharing out over 64 lanes: T (2P + 1) model
+    // evaluations per pass, an exponential counted twice. Below ~400 of them (C1: a quadratic over 10 timepoints = 70)
+    // the wave kernel's per-iteration synchronisation outweighs what it shares, whatever the voxel count: 512 voxels
+    // of C1 take 0.058 ms on the lane kernel against 0.105 ms.
+    return !(g_variant == 0 && cfg->noise == FVB_NOISE_WHITE && cfg->n_voxels < WAVE_KERNEL_BELOW_VOXELS && evaluations >= 400
+        && wave_layout(cfg->n_times, cfg->n_params, cfg->n_phis).bytes <= 160 * 1024);
+}
+
+LaneKernelInfo select_builtin_lane(const fvb_config *cfg)
+{
+    if (g_variant == 2 || (cfg->n_phis != 1 && cfg->noise == FVB_NOISE_WHITE && cfg->n_phis > 4))
         return LaneKernelInfo{ nullptr, 0, nullptr };
     if (cfg->noise == FVB_NOISE_AR1 && cfg->n_phis == 2) // two echoes: the two-pass kernel of vb_lane_arn_kernel.h
     {
@@ -175,13 +223,8 @@ LaneKernelInfo select_lane(const fvb_config *cfg)
     }
     if (cfg->n_phis != 1 && cfg->noise != FVB_NOISE_WHITE)
         return LaneKernelInfo{ nullptr, 0, nullptr };
-    // ... for models whose re-linearisation is long enough to be worth sharing out over 64 lanes: T (2P + 1) model
-    // evaluations per pass, an exponential counted twice. Below ~400 of them (C1: a quadratic over 10 timepoints = 70)
-    // the wave kernel's per-iteration synchronisation outweighs what it shares, whatever the voxel count: 512 voxels
-    // of C1 take 0.058 ms on the lane kernel against 0.105 ms.
     const double evaluations = (double)cfg->n_times * (2 * cfg->n_params + 1) * (cfg->model == FVB_MODEL_EXP ? 2.0 : 1.0);
-    if (g_variant == 0 && cfg->noise == FVB_NOISE_WHITE && cfg->n_voxels < WAVE_KERNEL_BELOW_VOXELS && evaluations >= 400
-        && wave_layout(cfg->n_times, cfg->n_params, cfg->n_phis).bytes <= 160 * 1024)
+    if (!lane_worth_it(cfg, evaluations))
         return LaneKernelInfo{ nullptr, 0, nullptr };
     const bool need_f = cfg->need_f != 0;
     if (cfg->noise == FVB_NOISE_WHITE && cfg->n_phis > 1) // noise-pattern: 2 .. 4 precisions
@@ -226,6 +269,26 @@ LaneKernelInfo select_lane(const fvb_config *cfg)
     default:
         return LaneKernelInfo{ nullptr, 0, nullptr };
     }
+}
+
+LaneRoute select_lane(const fvb_config *cfg)
+{
+    LaneRoute route;
+    if (cfg->model != FVB_MODEL_PLUGIN)
+    {
+        route.k = select_builtin_lane(cfg);
+        return route;
+    }
+    // A body from a model library: its lane kernels exist for white noise with one precision and for the parameter
+    // counts its library registered; the wave-per-voxel kernels of the body take everything else (a body's evaluation
+    // is counted once in the size rule).
+    if (g_variant == 2 || cfg->noise != FVB_NOISE_WHITE || cfg->n_phis != 1
+        || !lane_worth_it(cfg, (double)cfg->n_times * (2 * cfg->n_params + 1)))
+        return route;
+    int save_rows = 0;
+    if (find_device_lane_model(config_device_model(cfg), cfg->n_params, &route.launch, &save_rows))
+        route.k.save_rows = save_rows;
+    return route;
 }
 
 bool needs_save(const fvb_config *cfg)
@@ -638,18 +701,81 @@ const char *fabber_vb_device_model_name(int32_t i)
     return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->name : nullptr;
 }
 
+int32_t fabber_vb_register_device_lane_model(const fvb_device_lane_model *model)
+{
+    if (!model || !model->name || !model->name[0] || !model->launch)
+        return fail(-70, "fabber_vb_register_device_lane_model: descriptor, name or launcher is NULL");
+    const std::string name = model->name;
+    if (name.size() >= FVB_DEVICE_MODEL_NAME_MAX)
+        return fail(-70, "device lane model '" + name + "': the name is longer than " + std::to_string(FVB_DEVICE_MODEL_NAME_MAX - 1) + " characters");
+    if (model->abi_version != FVB_ABI_VERSION)
+        return fail(-71, "device lane model '" + name + "' was built for ABI version " + std::to_string(model->abi_version) + ", the engine is version "
+                + std::to_string(FVB_ABI_VERSION));
+    if (model->kernel_args_size != sizeof(KernelArgs))
+        return fail(-72, "device lane model '" + name + "': struct size mismatch (KernelArgs " + std::to_string(model->kernel_args_size) + " against "
+                + std::to_string(sizeof(KernelArgs)) + " bytes): the library was compiled against other kernel headers");
+    if (model->n_params < 1 || model->n_params > 6 || model->save_rows < 0)
+        return fail(-70, "device lane model '" + name + "': " + std::to_string(model->n_params)
+                + " parameters (the lane kernels of a library body exist for 1 to 6)");
+    DeviceLaneModelRegistry &r = device_lane_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    for (const fvb_device_lane_model *m : r.models)
+        if (m->n_params == model->n_params && name == m->name)
+            return fail(-73, "lane kernels of a device model named '" + name + "' with " + std::to_string(model->n_params)
+                    + " parameters are already registered");
+    r.models.push_back(model);
+    return 0;
+}
+
+int32_t fabber_vb_unregister_device_lane_model(const char *name, int32_t n_params)
+{
+    if (!name)
+        return fail(-70, "fabber_vb_unregister_device_lane_model: name is NULL");
+    DeviceLaneModelRegistry &r = device_lane_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    for (size_t i = 0; i < r.models.size(); i++)
+        if (r.models[i]->n_params == n_params && strcmp(r.models[i]->name, name) == 0)
+        {
+            r.models.erase(r.models.begin() + (long)i);
+            return 0;
+        }
+    return fail(-74, std::string("no lane kernels of a device model '") + name + "' with " + std::to_string(n_params) + " parameters are registered");
+}
+
+int32_t fabber_vb_device_lane_model_count(void)
+{
+    DeviceLaneModelRegistry &r = device_lane_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    return (int32_t)r.models.size();
+}
+
+const char *fabber_vb_device_lane_model_name(int32_t i)
+{
+    DeviceLaneModelRegistry &r = device_lane_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->name : nullptr;
+}
+
+int32_t fabber_vb_device_lane_model_params(int32_t i)
+{
+    DeviceLaneModelRegistry &r = device_lane_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->n_params : 0;
+}
+
 const char *fabber_vb_kernel_name(const fvb_config *cfg)
 {
     if (validate(cfg) != 0)
         return "invalid";
+    const LaneRoute route = select_lane(cfg);
     if (cfg->model == FVB_MODEL_PLUGIN)
     {
-        g_kernel_name = "wave<" + config_device_model(cfg) + ">";
+        g_kernel_name = route.launch ? "lane<" + config_device_model(cfg) + "," + std::to_string(cfg->n_params) + (cfg->need_f ? ",F>" : ">")
+                                     : "wave<" + config_device_model(cfg) + ">";
         return g_kernel_name.c_str();
     }
-    LaneKernelInfo k = select_lane(cfg);
-    if ((k.fn || k.fn_tiles_f32) && g_variant != 2)
-        return k.name;
+    if (route.any() && g_variant != 2)
+        return route.k.name;
     return "wave";
 }
 
@@ -705,19 +831,21 @@ int run_device_as(const fvb_config *cfg, const void *data, const fvb_outputs *ou
 
     fvb_config choice = *cfg;
     choice.n_voxels = kernel_voxels;
-    LaneKernelInfo lk = select_lane(&choice);
+    const LaneRoute route = select_lane(&choice);
+    const LaneKernelInfo &lk = route.k;
+    // (a library's lane kernels: all three feeds, as FVB_LANE_CASE instantiates them)
+    const bool has_strided = lk.fn || route.launch, has_tiles = lk.fn_tiles_f32 || route.launch;
     auto work_alloc = [&](void **p, size_t bytes) { return slot ? slot->take(p, bytes) : api_pool_alloc(p, bytes, stream); };
-    if (lk.fn || lk.fn_tiles_f32)
+    if (route.any())
     {
         if (needs_save(cfg))
             FVB_HIP_CHECK(work_alloc((void **)&ka.save, sizeof(double) * (size_t)lk.save_rows * cfg->n_voxels));
-        const unsigned grid = (unsigned)((cfg->n_voxels + 63) / 64);
-        LaneKernelFn fn = lk.fn;
+        int feed = LANE_FEED_STRIDED;
         void *tiles = nullptr;
         // White noise, no masked timepoints: the series is re-laid per wavefront once (one read and one
         // write of the image) and every pass of the voxel loop streams that block (vb_lane_kernel.h).
         // (the AR(1) kernels exist for the tiled series only)
-        if (lk.fn_tiles_f32 && (!lk.fn || (n_unmasked == cfg->n_times && g_residual_mode != 1 && g_tiled)))
+        if (has_tiles && (!has_strided || (n_unmasked == cfg->n_times && g_residual_mode != 1 && g_tiled)))
         {
             const int V = cfg->n_voxels, T = cfg->n_times;
             const unsigned rgrid = (unsigned)((V + 255) / 256);
@@ -725,21 +853,32 @@ int run_device_as(const fvb_config *cfg, const void *data, const fvb_outputs *ou
             {
                 FVB_HIP_CHECK(work_alloc(&tiles, Tile<double>::bytes(V, T)));
                 hipLaunchKernelGGL(retile_series<double>, dim3(rgrid), dim3(256), 0, stream, (const double *)data, (double *)tiles, V, T);
-                fn = (cfg->convergence == FVB_CONV_MAXITS && lk.fn_tiles_f64_counting) ? lk.fn_tiles_f64_counting : lk.fn_tiles_f64;
+                feed = LANE_FEED_TILES_F64;
             }
             else
             {
                 FVB_HIP_CHECK(work_alloc(&tiles, Tile<float>::bytes(V, T)));
                 hipLaunchKernelGGL(retile_series<float>, dim3(rgrid), dim3(256), 0, stream, (const float *)data, (float *)tiles, V, T);
-                fn = (cfg->convergence == FVB_CONV_MAXITS && lk.fn_tiles_f32_counting) ? lk.fn_tiles_f32_counting : lk.fn_tiles_f32;
+                feed = LANE_FEED_TILES_F32;
             }
             FVB_HIP_CHECK(hipGetLastError());
             ka.tiles = tiles;
         }
         // (the several-precisions kernels keep the T class bytes of the noise pattern in dynamic LDS)
         const size_t lds = (cfg->noise == FVB_NOISE_WHITE && cfg->n_phis > 1) ? (size_t)((cfg->n_times + 15) & ~15) : 0;
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, stream, ka);
-        FVB_HIP_CHECK(hipGetLastError());
+        const bool counting = cfg->convergence == FVB_CONV_MAXITS;
+        if (route.launch) // the kernels live in the library's code object: its launcher starts the one for this feed
+        {
+            char msg[512];
+            msg[0] = 0;
+            rc = route.launch(&ka, feed, counting ? 1 : 0, (void *)stream, msg, (int32_t)sizeof(msg));
+            if (rc)
+                g_last_error = msg;
+        }
+        else
+            rc = launch_lane_kernel(lk, ka, feed, counting, lds, stream, g_last_error);
+        if (rc)
+            return rc;
         for (void *work : { tiles, (void *)ka.save })
             if (work && !slot)
                 FVB_HIP_CHECK(api_pool_free(work, stream));
@@ -1154,7 +1293,7 @@ int32_t fabber_vb_run_host(const fvb_config *cfg, const void *data, const fvb_ou
     fvb_config choice = *cfg;
     // (a library model's wave kernels take what they need from the block alone, like the lane kernels: piped as well)
     if (block > 0 && cfg->n_voxels >= 2 * block
-        && (select_lane(&choice).fn || select_lane(&choice).fn_tiles_f32 || cfg->model == FVB_MODEL_PLUGIN))
+        && (select_lane(&choice).any() || cfg->model == FVB_MODEL_PLUGIN))
         return run_host_pipelined(cfg, data, out, device, block);
     return run_host_block(cfg, data, out, device, 0, cfg->n_voxels, nullptr, cfg->n_voxels);
 }

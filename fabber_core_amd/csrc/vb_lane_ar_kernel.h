@@ -559,6 +559,9 @@ __global__ __launch_bounds__(64, lane_waves<P>()) void vb_lane_ar_kernel(const K
     ma.iopt0 = ka.cfg.model_iopt[0];
     ma.dopt0 = ka.cfg.model_dopt[0];
     ma.design = ka.cfg.design;
+    ma.consts = ka.cfg.model_consts; // read by a model library's body only (include/fabber_device_lane_model.h)
+    ma.n_consts = ka.cfg.n_model_consts;
+    ma.model = ka.cfg.model;
 
     VoxelState<P> st;
     ArMoments<P> mo;

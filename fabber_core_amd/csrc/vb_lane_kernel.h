@@ -1435,6 +1435,9 @@ __global__ __launch_bounds__(64, lane_waves<P>()) void vb_lane_kernel(const Kern
     ma.iopt0 = ka.cfg.model_iopt[0];
     ma.dopt0 = ka.cfg.model_dopt[0];
     ma.design = ka.cfg.design;
+    ma.consts = ka.cfg.model_consts; // read by a model library's body only (include/fabber_device_lane_model.h)
+    ma.n_consts = ka.cfg.n_model_consts;
+    ma.model = ka.cfg.model;
     // this wavefront's block of the tiled series, and this lane's slot in group 0 of it
     const RAW *wave_tile = (FEED == FEED_STRIDED) ? nullptr : (const RAW *)ka.tiles + (size_t)blockIdx.x * Tile<RAW>::block_elems(T);
     const RAW *lane_tile = (FEED == FEED_STRIDED) ? nullptr : wave_tile + (size_t)(v & 63) * Tile<RAW>::G;

@@ -79,6 +79,15 @@ def lib():
         L.fabber_vb_device_model_count.restype = C.c_int32
         L.fabber_vb_device_model_name.restype = C.c_char_p
         L.fabber_vb_device_model_name.argtypes = [C.c_int32]
+        L.fabber_vb_register_device_lane_model.restype = C.c_int32
+        L.fabber_vb_register_device_lane_model.argtypes = [C.POINTER(vbabi.FvbDeviceLaneModel)]
+        L.fabber_vb_unregister_device_lane_model.restype = C.c_int32
+        L.fabber_vb_unregister_device_lane_model.argtypes = [C.c_char_p, C.c_int32]
+        L.fabber_vb_device_lane_model_count.restype = C.c_int32
+        L.fabber_vb_device_lane_model_name.restype = C.c_char_p
+        L.fabber_vb_device_lane_model_name.argtypes = [C.c_int32]
+        L.fabber_vb_device_lane_model_params.restype = C.c_int32
+        L.fabber_vb_device_lane_model_params.argtypes = [C.c_int32]
         if L.fabber_vb_abi_version() != vbabi.FVB_ABI_VERSION:
             raise HipEngineError("libfabber_vb_hip.so ABI version mismatch: rebuild")
         _LIB = L
@@ -124,6 +133,23 @@ def register_device_model(descriptor):
 
 def unregister_device_model(name):
     _check(lib().fabber_vb_unregister_device_model(name.encode()))
+
+
+def device_lane_models():
+    """(name, parameter count) of the lane-kernel entries registered with the engine (include/fabber_device_lane_model.h)."""
+    L = lib()
+    return [(L.fabber_vb_device_lane_model_name(i).decode(), L.fabber_vb_device_lane_model_params(i))
+            for i in range(L.fabber_vb_device_lane_model_count())]
+
+
+def register_device_lane_model(descriptor):
+    """fabber_vb_register_device_lane_model with a vbabi.FvbDeviceLaneModel (the caller keeps it alive); raises with the
+    engine's message when the registration is refused."""
+    _check(lib().fabber_vb_register_device_lane_model(C.byref(descriptor)))
+
+
+def unregister_device_lane_model(name, n_params):
+    _check(lib().fabber_vb_unregister_device_lane_model(name.encode(), n_params))
 
 
 def kernel_name(holder):

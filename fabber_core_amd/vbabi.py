@@ -91,6 +91,14 @@ class FvbDeviceModel(C.Structure):
                 ("launch", LAUNCH_FN)]
 
 
+class FvbDeviceLaneModel(C.Structure):
+    """fvb_device_lane_model: the lane-per-voxel kernels of a device body for one parameter count
+    (include/fabber_device_lane_model.h)"""
+    LAUNCH_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32)
+    _fields_ = [("name", C.c_char_p), ("abi_version", C.c_int32), ("kernel_args_size", C.c_uint32), ("n_params", C.c_int32),
+                ("save_rows", C.c_int32), ("launch", LAUNCH_FN)]
+
+
 class FvbOutputs(C.Structure):
     _fields_ = [
         ("mvn", C.c_void_p),

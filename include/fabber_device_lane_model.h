@@ -1,0 +1,143 @@
+/*
+ * fabber_device_lane_model.h - the lane-per-voxel kernels for a model library's DEVICE body.
+ *
+ * fabber_device_model.h gives a body the wave-per-voxel kernels (one wavefront per voxel): any parameter count, every
+ * noise model, and about 3 M voxels/s at most. The lane-per-voxel kernels (one voxel per lane, 64 voxels per wavefront)
+ * are what the engine runs its built-in models on from a few thousand voxels up. This header compiles them around the
+ * SAME body, for one parameter count per macro line:
+ *
+ *     FABBER_DEVICE_MODEL("invrec", InvRec)          // the wave kernels: the route of everything not covered below
+ *     FABBER_DEVICE_LANE_MODEL("invrec", InvRec, 3)  // the lane kernels for exactly 3 parameters
+ *
+ * Several lines per name are allowed (a model with a variable parameter count names the counts worth having), each for
+ * 1 <= P <= 6. The first line is required: a lane entry without a wave body of the same name is never used. It is a
+ * header of its own because it includes the lane kernels: a library that does not want them does not pay for them.
+ * Compile as fabber_device_model.h says; a macro line takes some tens of seconds.
+ *
+ * The body is the struct of fabber_device_model.h, unchanged:
+ *
+ *     static __device__ __forceinline__ double eval(const fvb::ModelArgs &a, int P, int t, const double *p)
+ *
+ * Declare eval __forceinline__. The lane kernel keeps a voxel's parameter vector in registers and calls eval 2 P + 1
+ * times per timepoint; a body that is not inlined receives it through a pointer, which puts the vector into scratch
+ * memory for every call. Inlined, P is a constant and loops over it unroll.
+ *
+ * The engine takes the lane route for a configuration when a lane entry for (name, n_params) is registered, the noise
+ * is white with one precision, the kernel variant is not `wave`, and the size rule of the built-in models holds (variant
+ * `lane`, or at least 4096 voxels, or fewer than 400 model evaluations per pass). Everything else - noise patterns,
+ * AR(1) noise, other parameter counts, small volumes - runs the wave kernels of FABBER_DEVICE_MODEL. The body is
+ * evaluated pointwise, as in the wave kernels (a library cannot supply a sweep), and the kernel's name is
+ * lane<NAME,P> / lane<NAME,P,F>.
+ *
+ * The macro, at namespace scope:
+ *   - instantiates the eight white-noise lane kernels for the body (in-place feed, float tiles and double tiles, each
+ *     with and without the free energy, and the two tile-fed ones of a run whose detector only counts iterations);
+ *   - defines their launcher in this library's code object (one lane per voxel, the engine's error texts);
+ *   - registers { name, FVB_ABI_VERSION, sizeof(KernelArgs), P, rows of the save buffer, launcher } with the engine from
+ *     a static object whose destructor unregisters it. A refused registration (fabber_vb_last_error says why) leaves the
+ *     model on the wave kernels.
+ *
+ * The remarks of fabber_device_model.h about naming the body struct, linking and unloading apply.
+ */
+#ifndef FABBER_DEVICE_LANE_MODEL_H
+#define FABBER_DEVICE_LANE_MODEL_H
+
+#include "fabber_vb.h"
+#include "../fabber_core_amd/csrc/vb_lane_launch.h"
+
+#include <cstdio>
+#include <cstring>
+#include <string>
+
+namespace fvb
+{
+// the body as a model of the lane kernels (vb_models.h): P a constant, the pointwise sweep, the initial posterior from
+// the host (init_mvn)
+template <class Eval>
+struct LibraryLane
+{
+    template <int P>
+    struct Model
+    {
+        static constexpr bool host_evaluated = false;
+        static constexpr int model_id = FVB_MODEL_PLUGIN;
+        typedef PointwiseSweep<Model<P>, P> Sweep;
+        static __device__ __forceinline__ double eval(const ModelArgs &a, int t, const double (&p)[P])
+        {
+            return Eval::eval(a, P, t, p);
+        }
+        static __device__ __forceinline__ void init_posterior(const ModelArgs &, double, double (&)[P])
+        {
+        }
+        static constexpr bool needs_data_max = false;
+    };
+};
+
+typedef LaneKernelInfo (*LaneKernelsFn)(bool need_f);
+
+inline int32_t device_lane_model_launch(LaneKernelsFn kernels, const void *kernel_args, int32_t feed, int32_t counting, void *stream,
+    char *err, int32_t err_len)
+{
+    const KernelArgs &ka = *static_cast<const KernelArgs *>(kernel_args);
+    std::string msg;
+    const int rc = launch_lane_kernel(kernels(ka.cfg.need_f != 0), ka, feed, counting != 0, 0, static_cast<hipStream_t>(stream), msg);
+    if (rc && err && err_len > 0)
+    {
+        strncpy(err, msg.c_str(), (size_t)err_len - 1);
+        err[err_len - 1] = 0;
+    }
+    return rc;
+}
+
+// registers in its constructor, unregisters in its destructor (the library's static object)
+struct DeviceLaneModelRegistration
+{
+    fvb_device_lane_model descriptor;
+    bool registered;
+    DeviceLaneModelRegistration(const char *name, int n_params, int save_rows, fvb_device_lane_launch_fn launch)
+    {
+        descriptor.name = name;
+        descriptor.abi_version = FVB_ABI_VERSION;
+        descriptor.kernel_args_size = (uint32_t)sizeof(KernelArgs);
+        descriptor.n_params = n_params;
+        descriptor.save_rows = save_rows;
+        descriptor.launch = launch;
+        registered = fabber_vb_register_device_lane_model(&descriptor) == 0;
+        if (!registered)
+            fprintf(stderr, "fabber: lane kernels of device model '%s' (%d parameters) not registered (%s): the model runs on the wave kernels\n",
+                name, n_params, fabber_vb_last_error());
+    }
+    ~DeviceLaneModelRegistration()
+    {
+        if (registered)
+            (void)fabber_vb_unregister_device_lane_model(descriptor.name, descriptor.n_params);
+    }
+    DeviceLaneModelRegistration(const DeviceLaneModelRegistration &) = delete;
+    DeviceLaneModelRegistration &operator=(const DeviceLaneModelRegistration &) = delete;
+};
+} // namespace fvb
+
+#define FABBER_DEVICE_LANE_MODEL_CAT2(a, b) a##b
+#define FABBER_DEVICE_LANE_MODEL_CAT(a, b) FABBER_DEVICE_LANE_MODEL_CAT2(a, b)
+// (FVB_LANE_CASE is the engine's own table entry of a built-in model: the same eight kernels, the same names)
+#define FABBER_DEVICE_LANE_MODEL(NAME, EVAL, NPARAMS)                                                                        \
+    static_assert((NPARAMS) >= 1 && (NPARAMS) <= 6, "FABBER_DEVICE_LANE_MODEL: the lane kernels of a library body exist for 1 to 6 parameters"); \
+    static fvb::LaneKernelInfo FABBER_DEVICE_LANE_MODEL_CAT(fabber_device_lane_kernels_, __LINE__)(bool need_f)              \
+    {                                                                                                                        \
+        using namespace fvb;                                                                                                 \
+        switch (NPARAMS)                                                                                                     \
+        {                                                                                                                    \
+            FVB_LANE_CASE(LibraryLane<EVAL>::Model, NAME, NPARAMS)                                                           \
+        }                                                                                                                    \
+        return LaneKernelInfo{ nullptr, 0, nullptr };                                                                        \
+    }                                                                                                                        \
+    static int32_t FABBER_DEVICE_LANE_MODEL_CAT(fabber_device_lane_launch_, __LINE__)(                                       \
+        const void *kernel_args, int32_t feed, int32_t counting, void *stream, char *err, int32_t err_len)                   \
+    {                                                                                                                        \
+        return fvb::device_lane_model_launch(&FABBER_DEVICE_LANE_MODEL_CAT(fabber_device_lane_kernels_, __LINE__), kernel_args, feed, \
+            counting, stream, err, err_len);                                                                                 \
+    }                                                                                                                        \
+    static fvb::DeviceLaneModelRegistration FABBER_DEVICE_LANE_MODEL_CAT(fabber_device_lane_registration_, __LINE__)(        \
+        NAME, NPARAMS, fvb::lane_save_rows<NPARAMS>(), &FABBER_DEVICE_LANE_MODEL_CAT(fabber_device_lane_launch_, __LINE__));
+
+#endif /* FABBER_DEVICE_LANE_MODEL_H */

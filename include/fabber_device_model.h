@@ -44,6 +44,10 @@
  *
  * The host side of the model announces the body through FwdModel::GetDeviceModel: spec.device_model = "invrec",
  * spec.constants = the constants.
+ *
+ * The lane-per-voxel kernels (one voxel per lane: the engine's throughput kernels, for white noise with one precision
+ * from a few thousand voxels up) are compiled around the same body by fabber_device_lane_model.h, one macro line per
+ * parameter count, next to the line above.
  */
 #ifndef FABBER_DEVICE_MODEL_H
 #define FABBER_DEVICE_MODEL_H

@@ -264,6 +264,33 @@ int32_t fabber_vb_unregister_device_model(const char *name);
 int32_t fabber_vb_device_model_count(void);
 const char *fabber_vb_device_model_name(int32_t i); /* NULL when i is out of range */
 
+/*
+ * The lane-per-voxel kernels for such a body (FABBER_DEVICE_LANE_MODEL in include/fabber_device_lane_model.h): a second,
+ * independent registry keyed by (name, n_params), 1 <= n_params <= 6. An entry is used only next to a body of the same
+ * name in the registry above, which stays the route for everything the lane kernels of a library do not cover (noise
+ * patterns, AR(1), other parameter counts, small volumes). The engine sets up the work buffers and the series feed as
+ * for a built-in model and `launch` starts the kernel for them: feed 0 = the caller's [t][voxel] image read in place,
+ * 1 = float tiles, 2 = double tiles; counting != 0 = the run's detector only counts iterations (tile feeds with the
+ * free energy). save_rows is the number of rows of the save buffer the kernels with an F-driven detector need. The
+ * refusals and the lifetime rules are those of fabber_vb_register_device_model.
+ */
+typedef int32_t (*fvb_device_lane_launch_fn)(const void *kernel_args, int32_t feed, int32_t counting, void *stream, char *err,
+                                             int32_t err_len);
+typedef struct fvb_device_lane_model
+{
+    const char *name;
+    int32_t abi_version;       /* FVB_ABI_VERSION the library was compiled against */
+    uint32_t kernel_args_size; /* sizeof(fvb::KernelArgs) */
+    int32_t n_params;
+    int32_t save_rows;
+    fvb_device_lane_launch_fn launch;
+} fvb_device_lane_model;
+int32_t fabber_vb_register_device_lane_model(const fvb_device_lane_model *model);
+int32_t fabber_vb_unregister_device_lane_model(const char *name, int32_t n_params);
+int32_t fabber_vb_device_lane_model_count(void);
+const char *fabber_vb_device_lane_model_name(int32_t i); /* NULL when i is out of range */
+int32_t fabber_vb_device_lane_model_params(int32_t i);   /* 0 when i is out of range */
+
 /* Which kernel a configuration would dispatch to ("lane<exp,4>" / "wave" / "wave<NAME>" for a registered body ...). */
 const char *fabber_vb_kernel_name(const fvb_config *cfg);
 
