@@ -25,6 +25,8 @@ struct NLLSInferenceTechnique::EngineStorage
     vector<unsigned char> phi_index;
     vector<Parameter> params;
     bool host_model = false;
+    bool library_device_model = false; // the model runs on the device with a body and NLLS minimisers of its own library (FVB_MODEL_PLUGIN)
+    vector<double> constants;          // ... and its constants (fvb_config.model_consts)
     // more than FVB_MAX_PARAMS parameters: the per-parameter entries as a table (fvb_config.params_ext)
     vector<int32_t> wide_transform, wide_type;
     vector<double> wide_zero, wide_post_mean;
@@ -36,7 +38,7 @@ static OptionSpec NLLS_OPTIONS[] = {
     { "vb-init", OPT_BOOL, "Whether NLLS is being run in isolation or as a pre-step for VB", OPT_NONREQ, "" },
     { "lm", OPT_BOOL, "Whether to use LM convergence (default is L)", OPT_NONREQ, "" },
     { "host-model-threads", OPT_INT, "Host threads evaluating a host-side model (0 = as many as the hardware has, at most 16)", OPT_NONREQ, "0" },
-    { "host-model", OPT_BOOL, "Evaluate the forward model on the host even if it has a device body (always the case for models from a model library)", OPT_NONREQ, "" },
+    { "host-model", OPT_BOOL, "Evaluate the forward model on the host even if it has a device body (always the case for models from a model library without NLLS kernels for a device body)", OPT_NONREQ, "" },
     { "" },
 };
 
@@ -129,14 +131,40 @@ void NLLSInferenceTechnique::DoCalculations(FabberRunData &rundata)
     DeviceModelSpec spec;
     // A model without a device body (any model library written for the reference), or any model when host-model is
     // set, is evaluated on the host - the minimiser's iterations stay on the GPU (fabber_nlls_run_hostmodel_host).
-    // (a body registered by the model's library exists for voxelwise VB only: the host here)
-    const bool device_model = m_model->GetDeviceModel(spec) && spec.device_model.empty() && !rundata.GetBool("host-model");
+    bool device_model = m_model->GetDeviceModel(spec) && !rundata.GetBool("host-model");
+    // A body the model's library registered counts when the library also registered NLLS minimisers for it
+    // (include/fabber_device_nlls_model.h): the engine names a kernel for the configuration then. Without them - a
+    // library built for voxelwise VB only - the model is evaluated on the host, as before.
+    st.library_device_model = false;
+    st.constants.clear();
+    if (device_model && !spec.device_model.empty())
+    {
+        if (!wide && spec.device_model.size() < sizeof(cfg.device_model))
+        {
+            cfg.model = FVB_MODEL_PLUGIN;
+            strncpy(cfg.device_model, spec.device_model.c_str(), sizeof(cfg.device_model) - 1);
+            st.constants = spec.constants;
+            cfg.model_consts = st.constants.empty() ? NULL : st.constants.data();
+            cfg.n_model_consts = (int32_t)st.constants.size();
+            st.library_device_model = fabber_nlls_kernel_name(&cfg)[0] != 0;
+        }
+        if (st.library_device_model)
+            spec.model = FVB_MODEL_PLUGIN;
+        else
+        {
+            memset(cfg.device_model, 0, sizeof(cfg.device_model));
+            cfg.model_consts = NULL;
+            cfg.n_model_consts = 0;
+            device_model = false;
+        }
+    }
     if (!device_model)
     {
         spec = DeviceModelSpec();
         spec.model = FVB_MODEL_HOSTJAC;
     }
-    st.host_model = !device_model;
+    // (model fit and residuals of a library's model come from its host code, as under VB)
+    st.host_model = !device_model || st.library_device_model;
     cfg.model = spec.model;
     for (int i = 0; i < 4; i++)
     {
@@ -209,7 +237,12 @@ void NLLSInferenceTechnique::DoCalculations(FabberRunData &rundata)
     const int device = rundata.GetIntDefault("device", 0, 0);
     int rc;
     if (device_model)
+    {
+        if (st.library_device_model)
+            LOG << "NLLSInferenceTechnique::the model runs on the device with the body '" << cfg.device_model << "' of its library, kernel "
+                << fabber_nlls_kernel_name(&cfg) << endl;
         rc = fabber_nlls_run_host(&cfg, &nl, series, &out, device);
+    }
     else
     {
         HostModelContext ctx = { this, m_model, &rundata, NULL, &coords, &rundata.GetVoxelSuppData(), cfg.n_times, cfg.n_params, "", {} };

@@ -1,11 +1,14 @@
 /*
  * vb_nlls.hip - instantiations and C ABI of the non-linear least squares kernel
- * (vb_nlls_kernel.h; method=nlls, inference_nlls.cc).
+ * (vb_nlls_kernel.h; method=nlls, inference_nlls.cc), and the registry of the minimisers that model libraries compile
+ * around their device bodies (include/fabber_device_nlls_model.h).
  */
-#include "vb_nlls_kernel.h"
+#include "vb_nlls_launch.h"
 
 #include "vb_host_stage.h"
 
+#include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -58,9 +61,62 @@ NllsKernelInfo get_nlls_kernel(int model, int P)
 
 namespace
 {
-int validate_nlls(const fvb_config *cfg, const fvb_nlls *nl)
+// The NLLS minimisers of device bodies that model libraries have registered (include/fabber_device_nlls_model.h), by
+// (name, parameter count; 0 = the wave-per-voxel minimiser). The descriptors are the libraries' own static objects, as in
+// the registries of vb_api.hip.
+struct DeviceNllsModelRegistry
 {
-    if (!cfg || !nl)
+    std::mutex lock;
+    std::vector<const fvb_device_nlls_model *> models;
+};
+DeviceNllsModelRegistry &device_nlls_models()
+{
+    static DeviceNllsModelRegistry *r = new DeviceNllsModelRegistry; // (never destroyed: libraries unregister from static destructors)
+    return *r;
+}
+// (copies the launcher while the registry is locked: a descriptor may be unregistered by another thread at any time)
+bool find_device_nlls_model(const std::string &name, int n_params, fvb_device_nlls_launch_fn *launch)
+{
+    DeviceNllsModelRegistry &r = device_nlls_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    for (const fvb_device_nlls_model *m : r.models)
+        if (m->n_params == n_params && name == m->name)
+        {
+            *launch = m->launch;
+            return true;
+        }
+    return false;
+}
+std::string entry_text(const std::string &name, int n_params)
+{
+    return n_params == 0 ? "the wave NLLS minimiser of a device model named '" + name + "'"
+                         : "the lane NLLS minimiser of a device model named '" + name + "' with " + std::to_string(n_params) + " parameters";
+}
+bool device_model_registered(const std::string &name)
+{
+    for (int i = 0; i < fabber_vb_device_model_count(); i++)
+    {
+        const char *n = fabber_vb_device_model_name(i);
+        if (n && name == n)
+            return true;
+    }
+    return false;
+}
+
+// what a configuration runs on
+struct NllsRoute
+{
+    bool lane = false;
+    NllsKernelInfo builtin = { nullptr, nullptr };  // the built-in model's lane minimiser, if it has one for the count
+    fvb_device_nlls_launch_fn library = nullptr;    // FVB_MODEL_PLUGIN: the launcher of the entry taken
+    std::string name;                               // fabber_nlls_kernel_name
+};
+
+// the configuration's side of the checks, and the route
+// (nl: the minimiser's settings, checked where a run checks them; NULL = the configuration alone)
+int select_nlls(const fvb_config *cfg, NllsRoute &route, const fvb_nlls *nl = nullptr)
+{
+    if (!cfg)
         return api_fail(-1, "config is NULL");
     if (cfg->abi_version != FVB_ABI_VERSION)
         return api_fail(-2, "fvb_config.abi_version mismatch");
@@ -74,15 +130,49 @@ int validate_nlls(const fvb_config *cfg, const fvb_nlls *nl)
         return api_fail(-11, "exp model: n_params != 2 * num-exps");
     if (cfg->model == FVB_MODEL_POLY && (cfg->n_params != cfg->model_iopt[0] + 1))
         return api_fail(-12, "poly model: n_params != degree + 1");
-    if (nl->max_iterations < 0 || !(nl->lambda0 > 0) || !(nl->lambda_max > 0))
+    if (nl && (nl->max_iterations < 0 || !(nl->lambda0 > 0) || !(nl->lambda_max > 0)))
         return api_fail(-60, "bad minimiser settings");
+    const bool wave_fits = nlls_wave_layout(*cfg).bytes <= WAVE_LDS_PER_WORKGROUP_MAX;
+    const char *no_kernel = "no NLLS kernel for this problem: no lane instantiation for the model / parameter count and the "
+                            "series does not fit the 160 KB of LDS the wave-per-voxel kernel needs";
+    if (cfg->model == FVB_MODEL_PLUGIN) // a body of a model library: with the NLLS entries its library registered
+    {
+        const std::string name(cfg->device_model, strnlen(cfg->device_model, sizeof(cfg->device_model)));
+        if (name.empty())
+            return api_fail(-16, "FVB_MODEL_PLUGIN needs the name of a registered device model (fvb_config.device_model)");
+        if (!device_model_registered(name))
+            return api_fail(-16, "no device model '" + name + "' is registered (fabber_vb_register_device_model)");
+        if (cfg->n_model_consts < 0 || (cfg->n_model_consts > 0 && !cfg->model_consts))
+            return api_fail(-17, "device model '" + name + "': n_model_consts constants announced but model_consts is NULL");
+        fvb_device_nlls_launch_fn wave = nullptr, lane = nullptr;
+        if (!find_device_nlls_model(name, 0, &wave))
+            return api_fail(-61, "method=nlls needs a forward model with a device body");
+        const bool has_lane = cfg->n_params <= 6 && !cfg->params_ext && find_device_nlls_model(name, cfg->n_params, &lane);
+        route.lane = nlls_takes_lane(has_lane, api_variant(), *cfg);
+        if (!route.lane && !wave_fits)
+            return api_fail(-61, no_kernel);
+        route.library = route.lane ? lane : wave;
+        route.name = route.lane ? "nlls<" + name + "," + std::to_string(cfg->n_params) + ">" : "nlls_wave<" + name + ">";
+        return 0;
+    }
     if (cfg->model != FVB_MODEL_POLY && cfg->model != FVB_MODEL_LINEAR && cfg->model != FVB_MODEL_EXP)
         return api_fail(-61, "method=nlls needs a forward model with a device body");
-    if (!get_nlls_kernel(cfg->model, cfg->n_params).fn && wave_layout(cfg->n_times, cfg->n_params, 1).bytes > 160 * 1024)
-        return api_fail(-61, "no NLLS kernel for this problem: no lane instantiation for the model / parameter count and the "
-                             "series does not fit the 160 KB of LDS the wave-per-voxel kernel needs");
+    if (!cfg->params_ext)
+        route.builtin = get_nlls_kernel(cfg->model, cfg->n_params);
+    if (!route.builtin.fn && !wave_fits)
+        return api_fail(-61, no_kernel);
+    route.lane = nlls_takes_lane(route.builtin.fn != nullptr, api_variant(), *cfg);
+    route.name = route.lane ? route.builtin.name : "nlls_wave";
     return 0;
 }
+
+int validate_nlls(const fvb_config *cfg, const fvb_nlls *nl, NllsRoute &route)
+{
+    if (!cfg || !nl)
+        return api_fail(-1, "config is NULL");
+    return select_nlls(cfg, route, nl);
+}
+thread_local std::string g_nlls_kernel_name;
 } // namespace
 
 extern "C" {
@@ -96,10 +186,82 @@ void fabber_nlls_defaults(fvb_nlls *nl)
     nl->lambda_max = 1e20;
 }
 
+int32_t fabber_vb_register_device_nlls_model(const fvb_device_nlls_model *model)
+{
+    if (!model || !model->name || !model->name[0] || !model->launch)
+        return api_fail(-70, "fabber_vb_register_device_nlls_model: descriptor, name or launcher is NULL");
+    const std::string name = model->name;
+    if (name.size() >= FVB_DEVICE_MODEL_NAME_MAX)
+        return api_fail(-70, "device NLLS model '" + name + "': the name is longer than " + std::to_string(FVB_DEVICE_MODEL_NAME_MAX - 1) + " characters");
+    if (model->abi_version != FVB_ABI_VERSION)
+        return api_fail(-71, "device NLLS model '" + name + "' was built for ABI version " + std::to_string(model->abi_version) + ", the engine is version "
+                + std::to_string(FVB_ABI_VERSION));
+    if (model->nlls_args_size != sizeof(NllsArgs) || model->wave_layout_size != sizeof(WaveLayout))
+        return api_fail(-72, "device NLLS model '" + name + "': struct size mismatch (NllsArgs " + std::to_string(model->nlls_args_size) + " against "
+                + std::to_string(sizeof(NllsArgs)) + " bytes, WaveLayout " + std::to_string(model->wave_layout_size) + " against "
+                + std::to_string(sizeof(WaveLayout)) + "): the library was compiled against other kernel headers");
+    if (model->n_params < 0 || model->n_params > 6)
+        return api_fail(-70, "device NLLS model '" + name + "': " + std::to_string(model->n_params)
+                + " parameters (0 = the wave minimiser; the lane minimisers of a library body exist for 1 to 6)");
+    DeviceNllsModelRegistry &r = device_nlls_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    for (const fvb_device_nlls_model *m : r.models)
+        if (m->n_params == model->n_params && name == m->name)
+            return api_fail(-73, entry_text(name, model->n_params) + " is already registered");
+    r.models.push_back(model);
+    return 0;
+}
+
+int32_t fabber_vb_unregister_device_nlls_model(const char *name, int32_t n_params)
+{
+    if (!name)
+        return api_fail(-70, "fabber_vb_unregister_device_nlls_model: name is NULL");
+    DeviceNllsModelRegistry &r = device_nlls_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    for (size_t i = 0; i < r.models.size(); i++)
+        if (r.models[i]->n_params == n_params && strcmp(r.models[i]->name, name) == 0)
+        {
+            r.models.erase(r.models.begin() + (long)i);
+            return 0;
+        }
+    return api_fail(-74, entry_text(name, n_params) + " is not registered");
+}
+
+int32_t fabber_vb_device_nlls_model_count(void)
+{
+    DeviceNllsModelRegistry &r = device_nlls_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    return (int32_t)r.models.size();
+}
+
+const char *fabber_vb_device_nlls_model_name(int32_t i)
+{
+    DeviceNllsModelRegistry &r = device_nlls_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->name : nullptr;
+}
+
+int32_t fabber_vb_device_nlls_model_params(int32_t i)
+{
+    DeviceNllsModelRegistry &r = device_nlls_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->n_params : -1;
+}
+
+const char *fabber_nlls_kernel_name(const fvb_config *cfg)
+{
+    NllsRoute route;
+    if (select_nlls(cfg, route) != 0)
+        return "";
+    g_nlls_kernel_name = route.name;
+    return g_nlls_kernel_name.c_str();
+}
+
 int32_t fabber_nlls_run_device(const fvb_config *cfg, const fvb_nlls *nl, const void *data, const fvb_outputs *out,
     void *stream, int32_t n_unmasked)
 {
-    int rc = validate_nlls(cfg, nl);
+    NllsRoute route;
+    int rc = validate_nlls(cfg, nl, route);
     if (rc)
         return rc;
     if (!out || !out->mvn)
@@ -115,31 +277,23 @@ int32_t fabber_nlls_run_device(const fvb_config *cfg, const fvb_nlls *nl, const 
     na.ka.data = data;
     na.ka.n_unmasked = n_unmasked;
     na.nl = *nl;
-    const NllsKernelInfo k = get_nlls_kernel(cfg->model, cfg->n_params);
-    const WaveLayout L = wave_layout(cfg->n_times, cfg->n_params, 1);
-    // lane per voxel where an instantiation exists and there are enough voxels to fill the chip
-    // (as the VB kernels, vb_api.cc); wave per voxel otherwise
-    const bool wave_fits = L.bytes <= 160 * 1024;
-    const int variant = api_variant();
-    if (k.fn && variant != 2 && (variant == 1 || cfg->n_voxels >= 4096 || !wave_fits))
+    if (route.library) // the minimiser lives in the model library's code object
     {
-        const unsigned grid = (unsigned)((cfg->n_voxels + 63) / 64);
-        hipLaunchKernelGGL(k.fn, dim3(grid), dim3(64), 0, (hipStream_t)stream, na);
+        char err[512] = "";
+        rc = route.library(&na, stream, err, (int32_t)sizeof(err));
+        return rc ? api_fail(rc, err[0] ? err : "the NLLS launcher of the device model failed") : 0;
     }
-    else
-    {
-        if (L.bytes > 64 * 1024)
-            FVB_HIP_CHECK(hipFuncSetAttribute((const void *)nlls_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes));
-        hipLaunchKernelGGL(nlls_wave_kernel, dim3((unsigned)cfg->n_voxels), dim3(64), L.bytes, (hipStream_t)stream, na, L);
-    }
-    FVB_HIP_CHECK(hipGetLastError());
-    return 0;
+    std::string err;
+    rc = launch_nlls_kernel(route.builtin.fn, nlls_wave_kernel<BuiltinEval>, route.lane ? NLLS_VARIANT_LANE : NLLS_VARIANT_WAVE, na,
+        (hipStream_t)stream, err);
+    return rc ? api_fail(rc, err) : 0;
 }
 
 int32_t fabber_nlls_run_host(const fvb_config *cfg, const fvb_nlls *nl, const void *data, const fvb_outputs *out,
     int32_t device)
 {
-    int rc = validate_nlls(cfg, nl);
+    NllsRoute route;
+    int rc = validate_nlls(cfg, nl, route);
     if (rc)
         return rc;
     if (!out || !out->mvn)

@@ -57,6 +57,9 @@ __global__ __launch_bounds__(64, 2) void nlls_lane_kernel(const NllsArgs na)
     ma.iopt0 = ka.cfg.model_iopt[0];
     ma.dopt0 = ka.cfg.model_dopt[0];
     ma.design = ka.cfg.design;
+    ma.consts = ka.cfg.model_consts; // read by a model library's body only (include/fabber_device_nlls_model.h)
+    ma.n_consts = ka.cfg.n_model_consts;
+    ma.model = ka.cfg.model;
 
     // starting estimate, Fabber space (inference_nlls.cc:131-132: the means of the 'posterior'
     // from HardcodedInitialDists or fwd-inital-posterior are used as they are)
@@ -392,6 +395,9 @@ __device__ __forceinline__ void nlls_wave_stage(const KernelArgs &ka, WaveCtx &c
     }
 }
 
+// Eval: what evaluates the model (vb_wave_kernel.h: BuiltinEval for the engine's own models, a model library's body
+// through include/fabber_device_nlls_model.h)
+template <class Eval>
 __global__ __launch_bounds__(64) void nlls_wave_kernel(const NllsArgs na, const WaveLayout L)
 {
     extern __shared__ double wave_lds[];
@@ -409,11 +415,7 @@ __global__ __launch_bounds__(64) void nlls_wave_kernel(const NllsArgs na, const 
     cx.sv_prec = false;
     double *sh = cx.sh;
 
-    ModelArgs ma;
-    ma.iopt0 = ka.cfg.model_iopt[0];
-    ma.dopt0 = ka.cfg.model_dopt[0];
-    ma.design = ka.cfg.design;
-    ma.model = ka.cfg.model;
+    const ModelArgs ma = wave_model_args(ka);
 
     nlls_wave_stage(ka, cx);
     FVB_WAVE_FOR(i, L.P)
@@ -421,7 +423,7 @@ __global__ __launch_bounds__(64) void nlls_wave_kernel(const NllsArgs na, const 
     wave_sync();
 
     NllsWaveState s;
-    s.status = wave_recentre(ka, ma, cx);
+    s.status = wave_recentre<Eval>(ka, ma, cx);
     s.cf = sh[L.s];
     nlls_wave_accept(cx);
     s.lambda = na.nl.lambda0;
@@ -431,7 +433,7 @@ __global__ __launch_bounds__(64) void nlls_wave_kernel(const NllsArgs na, const 
     while (s.running && s.niter < na.nl.max_iterations)
     {
         nlls_wave_propose(na.nl, cx, s);
-        const int st = wave_recentre(ka, ma, cx);
+        const int st = wave_recentre<Eval>(ka, ma, cx);
         nlls_wave_judge(na.nl, cx, s, st);
     }
     nlls_wave_finish(ka, cx, s);
@@ -439,6 +441,9 @@ __global__ __launch_bounds__(64) void nlls_wave_kernel(const NllsArgs na, const 
 
 // One launch = for every voxel of the batch: take the host's linearisation about the point asked for, judge it
 // (or, the first time, make it the starting point), then either ask for the next trial point or finish.
+// (the engine's own kernel, not a template: a model library, which includes this header in several of its sources for
+// the templates above, leaves it out - include/fabber_device_nlls_model.h defines FVB_NLLS_TEMPLATES_ONLY)
+#ifndef FVB_NLLS_TEMPLATES_ONLY
 __global__ __launch_bounds__(64) void nlls_wave_step_kernel(const NllsHmArgs ha)
 {
     extern __shared__ double wave_lds[];
@@ -516,6 +521,7 @@ __global__ __launch_bounds__(64) void nlls_wave_step_kernel(const NllsHmArgs ha)
         ha.phase_out[v] = sc.phase;
     }
 }
+#endif // FVB_NLLS_TEMPLATES_ONLY
 
 #endif // __HIPCC__
 } // namespace fvb

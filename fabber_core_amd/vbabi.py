@@ -99,6 +99,14 @@ class FvbDeviceLaneModel(C.Structure):
                 ("save_rows", C.c_int32), ("launch", LAUNCH_FN)]
 
 
+class FvbDeviceNllsModel(C.Structure):
+    """fvb_device_nlls_model: an NLLS minimiser of a device body - n_params = 0 the wave-per-voxel one, 1 to 6 the
+    lane-per-voxel one for that parameter count (include/fabber_device_nlls_model.h)"""
+    LAUNCH_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32)
+    _fields_ = [("name", C.c_char_p), ("abi_version", C.c_int32), ("nlls_args_size", C.c_uint32), ("wave_layout_size", C.c_uint32),
+                ("n_params", C.c_int32), ("launch", LAUNCH_FN)]
+
+
 class FvbOutputs(C.Structure):
     _fields_ = [
         ("mvn", C.c_void_p),

@@ -28,7 +28,8 @@
  * a.consts / a.n_consts are the model's constants (a list of inversion times, a dose, a TR): read-only device memory,
  * the same for every voxel, filled from DeviceModelSpec::constants (fvb_config.model_consts). The expression must be
  * the one the model's host EvaluateModel computes - the host code still provides the initial posterior, the result
- * images, and the whole fit wherever the device body is not used (spatial VB, method=nlls, the host-model option).
+ * images, and the whole fit wherever the device body is not used (spatial VB, the host-model option, and method=nlls
+ * unless the library also uses the macros of fabber_device_nlls_model.h).
  *
  * The macro, at namespace scope, once per model:
  *   - instantiates the white-noise kernel (with and without the free energy) and the four AR(1) kernels for the body;
@@ -47,7 +48,8 @@
  *
  * The lane-per-voxel kernels (one voxel per lane: the engine's throughput kernels, for white noise with one precision
  * from a few thousand voxels up) are compiled around the same body by fabber_device_lane_model.h, one macro line per
- * parameter count, next to the line above.
+ * parameter count, next to the line above. The NLLS minimisers of method=nlls (one wavefront or one lane per voxel, the
+ * whole minimisation in one launch) are compiled around it by fabber_device_nlls_model.h in the same way.
  */
 #ifndef FABBER_DEVICE_MODEL_H
 #define FABBER_DEVICE_MODEL_H

@@ -540,6 +540,38 @@ int32_t fabber_nlls_run_host(const fvb_config *cfg, const fvb_nlls *nl, const vo
 int32_t fabber_nlls_run_hostmodel_host(const fvb_config *cfg, const fvb_nlls *nl, const void *data, const fvb_outputs *out,
     int32_t device, fvb_linearise_fn linearise, void *user);
 
+/*
+ * The NLLS minimisers for a device body of a model library (FABBER_DEVICE_NLLS_MODEL / FABBER_DEVICE_NLLS_LANE_MODEL in
+ * include/fabber_device_nlls_model.h): a third, independent registry keyed by (name, n_params). n_params = 0 is the
+ * wave-per-voxel minimiser (any parameter count), 1 to 6 the lane-per-voxel minimiser for exactly that count. With a
+ * wave entry next to a body of the same name in the registry of fabber_vb_register_device_model, fabber_nlls_run_host /
+ * _device accept FVB_MODEL_PLUGIN for that name (-61 without it, as before); a lane entry is used only next to the wave
+ * entry, under the size rule of the built-in models. `launch` receives the engine's arguments (fvb::NllsArgs, sizeof =
+ * nlls_args_size; the wave launcher derives the LDS layout, sizeof(fvb::WaveLayout) = wave_layout_size, from them),
+ * launches the whole minimisation asynchronously on `stream` (a hipStream_t) and returns 0 or a negative code with its
+ * message in err. The refusals and the lifetime rules are those of fabber_vb_register_device_lane_model.
+ */
+typedef int32_t (*fvb_device_nlls_launch_fn)(const void *nlls_args, void *stream, char *err, int32_t err_len);
+typedef struct fvb_device_nlls_model
+{
+    const char *name;
+    int32_t abi_version;       /* FVB_ABI_VERSION the library was compiled against */
+    uint32_t nlls_args_size;   /* sizeof(fvb::NllsArgs) */
+    uint32_t wave_layout_size; /* sizeof(fvb::WaveLayout) */
+    int32_t n_params;          /* 0 = the wave-per-voxel minimiser, 1 to 6 = the lane-per-voxel minimiser for that count */
+    fvb_device_nlls_launch_fn launch;
+} fvb_device_nlls_model;
+int32_t fabber_vb_register_device_nlls_model(const fvb_device_nlls_model *model);
+int32_t fabber_vb_unregister_device_nlls_model(const char *name, int32_t n_params);
+int32_t fabber_vb_device_nlls_model_count(void);
+const char *fabber_vb_device_nlls_model_name(int32_t i); /* NULL when i is out of range */
+int32_t fabber_vb_device_nlls_model_params(int32_t i);   /* -1 when i is out of range */
+
+/* Which kernel fabber_nlls_run_* would take for a configuration: "nlls<exp,2>" / "nlls<NAME,P>" (lane per voxel),
+ * "nlls_wave" / "nlls_wave<NAME>" (wave per voxel), "" where the run would answer -61 (a model without a device body, a
+ * library body without an NLLS entry). Reads n_voxels, n_times, n_params, model and device_model. */
+const char *fabber_nlls_kernel_name(const fvb_config *cfg);
+
 /* The engine's work buffers (the re-laid series, the spatial run's state) come from the current device's
  * stream-ordered memory pool, which keeps them between runs (a caller that fits volume after volume allocates
  * once). This returns what the pool holds to the driver; the reference has no counterpart (host memory, freed by
