@@ -811,7 +811,18 @@ void Vb::DoCalculations(FabberRunData &rundata)
                 (int32_t)device_list.size(), spatial_progress);
         }
         else if (m_store->has_device_model)
+        {
+            const char *kernels = m_store->library_device_model ? fabber_vb_spatial_kernel_name(&cfg) : "";
+            if (kernels[0])
+            {
+                // the library brought spatial kernels for this parameter count and noise model; they know no model's
+                // InitVoxelPosterior: the initial posterior comes from the model's host code
+                LOG << "Vb::the model runs on the device with the body '" << cfg.device_model << "' of its library, kernels "
+                    << kernels << endl;
+                BuildInitialMvn(rundata, cfg);
+            }
             rc = fabber_vb_run_spatial_host(&cfg, &sp, series, &out, device, spatial_progress);
+        }
         if (m_store->has_device_model && rc == -40)
         {
             // no spatial kernels were built for this model with this many parameters: the model's own host code

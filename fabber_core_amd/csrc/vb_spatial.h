@@ -383,6 +383,9 @@ __global__ __launch_bounds__(64, lane_waves<P>()) void vb_spatial_setup_kernel(c
     ma.iopt0 = ka.cfg.model_iopt[0];
     ma.dopt0 = ka.cfg.model_dopt[0];
     ma.design = ka.cfg.design;
+    ma.consts = ka.cfg.model_consts; // read by a model library's body only (include/fabber_device_spatial_model.h)
+    ma.n_consts = ka.cfg.n_model_consts;
+    ma.model = ka.cfg.model;
     ma.exp_table = ACC ? exp_tab : nullptr;
     VoxelState<P> st;
     Moments<P> mo;
@@ -1411,6 +1414,9 @@ __global__ __launch_bounds__(64, lane_waves<P>()) void vb_spatial_noise_kernel(c
     ma.iopt0 = ka.cfg.model_iopt[0];
     ma.dopt0 = ka.cfg.model_dopt[0];
     ma.design = ka.cfg.design;
+    ma.consts = ka.cfg.model_consts; // read by a model library's body only (include/fabber_device_spatial_model.h)
+    ma.n_consts = ka.cfg.n_model_consts;
+    ma.model = ka.cfg.model;
     ma.exp_table = ACC ? exp_tab : nullptr;
     VoxelState<P> st;
     Moments<P> mo;

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -32,13 +33,92 @@ int fvb::spatial_noise_kind(const fvb_config *cfg)
 }
 const char *const fvb::spatial_noise_refusal
     = "spatial VB runs white noise with up to 8 noise precisions and AR(1) noise with one or two echoes";
-// the kernel table of a configuration (setup == NULL: none was built for this model / parameter count / noise model)
-static SpatialKernels spatial_kernels_for(const fvb_config *cfg)
+namespace
 {
-    const int kind = spatial_noise_kind(cfg), P = cfg->n_params;
+// The spatial kernels of device bodies that model libraries have registered (include/fabber_device_spatial_model.h), by
+// (name, parameter count). The descriptors are the libraries' own static objects, as in the registries of vb_api.hip.
+struct DeviceSpatialModelRegistry
+{
+    std::mutex lock;
+    std::vector<const fvb_device_spatial_model *> models;
+};
+DeviceSpatialModelRegistry &device_spatial_models()
+{
+    static DeviceSpatialModelRegistry *r = new DeviceSpatialModelRegistry; // (never destroyed: libraries unregister from static destructors)
+    return *r;
+}
+// (copies what a run needs while the registry is locked: a descriptor may be unregistered by another thread at any time)
+bool find_device_spatial_model(const std::string &name, int n_params, fvb_device_spatial_launch_fn *launch, int *state_rows)
+{
+    DeviceSpatialModelRegistry &r = device_spatial_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    for (const fvb_device_spatial_model *m : r.models)
+        if (m->n_params == n_params && name == m->name)
+        {
+            *launch = m->launch;
+            *state_rows = m->state_rows;
+            return true;
+        }
+    return false;
+}
+bool device_model_registered(const std::string &name)
+{
+    for (int i = 0; i < fabber_vb_device_model_count(); i++)
+    {
+        const char *n = fabber_vb_device_model_name(i);
+        if (n && name == n)
+            return true;
+    }
+    return false;
+}
+std::string spatial_entry_text(const std::string &name, int n_params)
+{
+    return "spatial kernels of a device model named '" + name + "' with " + std::to_string(n_params) + " parameters";
+}
+
+// What a configuration runs on: the kernel table, and for a body of a model library the launcher of its entry
+struct SpatialRoute
+{
+    SpatialKernels k{};
+    fvb_device_spatial_launch_fn library = nullptr;
+    std::string name; // fabber_vb_spatial_kernel_name
+    bool found() const
+    {
+        return k.setup != nullptr || library != nullptr;
+    }
+};
+thread_local std::string g_spatial_kernel_name;
+} // namespace
+
+// A body of a model library: the table of the parameter count with the engine's own kernels wherever the model plays no
+// part - the linear model's table serves, it covers 1 ... 8 parameters - and the three that evaluate the model left to
+// the library's launcher. Nothing (-40) without an entry for (name, P), under another noise model, or for a name without
+// a wave body (which the argument checks answer with -16 before this is asked).
+static SpatialRoute spatial_route_library(const fvb_config *cfg, int kind)
+{
+    SpatialRoute route;
+    const std::string name(cfg->device_model, strnlen(cfg->device_model, sizeof(cfg->device_model)));
+    fvb_device_spatial_launch_fn launch = nullptr;
+    int state_rows = 0;
+    if (kind != FVB_SPNZ_WHITE || cfg->params_ext || name.empty() || !device_model_registered(name)
+        || !find_device_spatial_model(name, cfg->n_params, &launch, &state_rows))
+        return route;
+    SpatialKernels k = get_spatial_kernels_linear(cfg->n_params, cfg->need_f != 0);
+    if (!k.setup || k.wave || k.lds_classes || k.state_rows != state_rows) // (state_rows: compiled against another SpLayout)
+        return route;
+    k.setup = k.noise = k.noise_fast = k.noise_acc = k.noise_fast_acc = nullptr; // the library's
+    route.name = "spatial<" + name + "," + std::to_string(cfg->n_params) + ">";
+    k.name = nullptr; // (route.name)
+    route.k = k;
+    route.library = launch;
+    return route;
+}
+
+// the kernel table of a configuration (none: no kernels were built for this model / parameter count / noise model)
+static SpatialKernels spatial_kernels_builtin(const fvb_config *cfg, int kind)
+{
+    const int P = cfg->n_params;
     const bool need_f = cfg->need_f != 0;
-    if (kind < 0)
-        return SpatialKernels{};
     if (kind >= FVB_SPNZ_ARN2 && kind <= FVB_SPNZ_ARN4)
         return get_spatial_kernels_nz_arn(cfg->model, P, need_f, kind);
     if (kind == FVB_SPNZ_PATTERN8)
@@ -57,7 +137,22 @@ static SpatialKernels spatial_kernels_for(const fvb_config *cfg)
         return SpatialKernels{};
     }
 }
+static SpatialRoute spatial_kernels_for(const fvb_config *cfg)
+{
+    const int kind = spatial_noise_kind(cfg);
+    if (kind < 0)
+        return SpatialRoute{};
+    if (cfg->model == FVB_MODEL_PLUGIN)
+        return spatial_route_library(cfg, kind);
+    SpatialRoute route;
+    route.k = spatial_kernels_builtin(cfg, kind);
+    if (route.k.setup && route.k.name)
+        route.name = route.k.name;
+    return route;
+}
 // what a configuration without a kernel table (-40) is told
+static const char *const spatial_init_mvn_refusal
+    = "a device model of a library needs the initial posterior as init_mvn (the model's InitVoxelPosterior runs on the host)";
 static std::string spatial_kernels_refusal(const fvb_config *cfg)
 {
     if (cfg->model == FVB_MODEL_HOSTJAC && cfg->n_params > 8 && spatial_noise_kind(cfg) != FVB_SPNZ_WHITE)
@@ -100,9 +195,15 @@ int fvb_spatial_run::open(const fvb_config *cfg_, const fvb_spatial *sp_, const 
         return api_fail(-45, "owned voxel range outside the local voxel list");
     if (spatial_noise_kind(&cfg) < 0)
         return api_fail(-44, spatial_noise_refusal);
-    k = spatial_kernels_for(&cfg);
-    if (!k.setup)
-        return api_fail(-40, spatial_kernels_refusal(&cfg));
+    {
+        const SpatialRoute route = spatial_kernels_for(&cfg);
+        if (!route.found())
+            return api_fail(-40, spatial_kernels_refusal(&cfg));
+        k = route.k;
+        library = route.library;
+    }
+    if (library && !cfg.init_mvn)
+        return api_fail(-52, spatial_init_mvn_refusal);
     if (cfg.model == FVB_MODEL_HOSTJAC && !lin_next) // (the kernels read the host's linearisations)
         return api_fail(-56, "a model evaluated on the host runs spatial VB through fabber_vb_run_spatial_hostmodel_host");
     noise_lds = k.lds_classes ? (size_t)cfg.n_times : 0;
@@ -171,10 +272,27 @@ int fvb_spatial_run::start_setup(const void *d_data, const fvb_outputs *d_out)
     FVB_HIP_CHECK(hipEventRecord(setup_done, stream));
     FVB_HIP_CHECK(hipStreamWaitEvent(setup_stream, setup_done, 0));
     // (the wave-per-voxel family: one workgroup per voxel)
-    hipLaunchKernelGGL(k.setup, dim3((unsigned)(k.wave ? V : (V + 63) / 64)), dim3(64), k.wave ? k.wave_lds : noise_lds,
-        setup_stream, sa);
-    FVB_HIP_CHECK(hipGetLastError());
+    const int rc = launch_model_kernel(FVB_SPATIAL_KERNEL_SETUP, k.setup, (unsigned)(k.wave ? V : (V + 63) / 64),
+        k.wave ? k.wave_lds : noise_lds, setup_stream);
+    if (rc)
+        return rc;
     FVB_HIP_CHECK(hipEventRecord(setup_done, setup_stream));
+    return 0;
+}
+
+// The three launches of a run that evaluate the model - set-up, the second sweep and the second sweep of the split form -
+// with the run's arguments `sa` by value: the engine's own kernel, or the launcher of a model library for the kernels
+// in its code object (64-lane workgroups either way)
+int fvb_spatial_run::launch_model_kernel(int which, SpatialKernelFn fn, unsigned grid, size_t lds, hipStream_t on)
+{
+    if (library)
+    {
+        char err[256] = "";
+        const int rc = library(which, cfg.need_f != 0, &sa, grid, (uint32_t)lds, on, err, (int32_t)sizeof(err));
+        return rc ? api_fail(rc, err[0] ? err : "the launcher of a device model's spatial kernels failed") : 0;
+    }
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, on, sa);
+    FVB_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
@@ -488,9 +606,8 @@ int fvb_spatial_run::sweep_noise(int it)
     sa.it = it;
     const int n_owned = owned_end - owned_begin;
     if (n_owned > 0)
-        hipLaunchKernelGGL(second_sweep(false, it), dim3((unsigned)(k.wave ? n_owned : (n_owned + 63) / 64)), dim3(64),
-            k.wave ? k.wave_lds : noise_lds, stream, sa);
-    FVB_HIP_CHECK(hipGetLastError());
+        return launch_model_kernel(FVB_SPATIAL_KERNEL_NOISE, second_sweep(false, it), (unsigned)(k.wave ? n_owned : (n_owned + 63) / 64),
+            k.wave ? k.wave_lds : noise_lds, stream);
     return 0;
 }
 
@@ -527,9 +644,7 @@ int fvb_spatial_run::fast_noise(int it)
 {
     sa.it = it;
     const int n_owned = owned_end - owned_begin;
-    hipLaunchKernelGGL(second_sweep(true, it), dim3((unsigned)((n_owned + 63) / 64)), dim3(64), noise_lds, stream, sa);
-    FVB_HIP_CHECK(hipGetLastError());
-    return 0;
+    return launch_model_kernel(FVB_SPATIAL_KERNEL_NOISE_SPLIT, second_sweep(true, it), (unsigned)((n_owned + 63) / 64), noise_lds, stream);
 }
 
 // This slab's top plane hands its new means to the bottom plane of `upper` (another device, or another stream of this
@@ -775,6 +890,79 @@ int run_spatial(const fvb_config *cfg, const fvb_spatial *sp, const void *d_data
 
 extern "C" {
 
+int32_t fabber_vb_register_device_spatial_model(const fvb_device_spatial_model *model)
+{
+    if (!model || !model->name || !model->name[0] || !model->launch)
+        return api_fail(-75, "fabber_vb_register_device_spatial_model: descriptor, name or launcher is NULL");
+    const std::string name = model->name;
+    if (name.size() >= FVB_DEVICE_MODEL_NAME_MAX)
+        return api_fail(-75, "device spatial model '" + name + "': the name is longer than " + std::to_string(FVB_DEVICE_MODEL_NAME_MAX - 1) + " characters");
+    if (model->abi_version != FVB_ABI_VERSION)
+        return api_fail(-76, "device spatial model '" + name + "' was built for ABI version " + std::to_string(model->abi_version) + ", the engine is version "
+                + std::to_string(FVB_ABI_VERSION));
+    if (model->spatial_args_size != sizeof(SpatialArgs))
+        return api_fail(-77, "device spatial model '" + name + "': struct size mismatch (SpatialArgs " + std::to_string(model->spatial_args_size) + " against "
+                + std::to_string(sizeof(SpatialArgs)) + " bytes): the library was compiled against other kernel headers");
+    if (model->n_params < 1 || model->n_params > 6)
+        return api_fail(-75, "device spatial model '" + name + "': " + std::to_string(model->n_params)
+                + " parameters (the spatial kernels of a library body exist for 1 to 6)");
+    DeviceSpatialModelRegistry &r = device_spatial_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    for (const fvb_device_spatial_model *m : r.models)
+        if (m->n_params == model->n_params && name == m->name)
+            return api_fail(-78, spatial_entry_text(name, model->n_params) + " are already registered");
+    r.models.push_back(model);
+    return 0;
+}
+
+int32_t fabber_vb_unregister_device_spatial_model(const char *name, int32_t n_params)
+{
+    if (!name)
+        return api_fail(-75, "fabber_vb_unregister_device_spatial_model: name is NULL");
+    DeviceSpatialModelRegistry &r = device_spatial_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    for (size_t i = 0; i < r.models.size(); i++)
+        if (r.models[i]->n_params == n_params && strcmp(r.models[i]->name, name) == 0)
+        {
+            r.models.erase(r.models.begin() + (long)i);
+            return 0;
+        }
+    return api_fail(-79, "no " + spatial_entry_text(name, n_params) + " are registered");
+}
+
+int32_t fabber_vb_device_spatial_model_count(void)
+{
+    DeviceSpatialModelRegistry &r = device_spatial_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    return (int32_t)r.models.size();
+}
+
+const char *fabber_vb_device_spatial_model_name(int32_t i)
+{
+    DeviceSpatialModelRegistry &r = device_spatial_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->name : nullptr;
+}
+
+int32_t fabber_vb_device_spatial_model_params(int32_t i)
+{
+    DeviceSpatialModelRegistry &r = device_spatial_models();
+    std::lock_guard<std::mutex> hold(r.lock);
+    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->n_params : 0;
+}
+
+// (the selection function of the run: "" where open() would answer -40 or -44)
+const char *fabber_vb_spatial_kernel_name(const fvb_config *cfg)
+{
+    if (!cfg || cfg->abi_version != FVB_ABI_VERSION || cfg->n_params <= 0)
+        return "";
+    const SpatialRoute route = spatial_kernels_for(cfg);
+    if (!route.found())
+        return "";
+    g_spatial_kernel_name = route.name;
+    return g_spatial_kernel_name.c_str();
+}
+
 // the argument checks of the device entry points
 static int32_t spatial_check_args(const fvb_config *cfg, const fvb_spatial *sp, const fvb_outputs *out)
 {
@@ -922,8 +1110,10 @@ static int32_t run_spatial_host_impl(const fvb_config *cfg, const fvb_spatial *s
     // series on the device twice)
     if (spatial_noise_kind(cfg) < 0)
         return api_fail(-44, spatial_noise_refusal);
-    if (!spatial_kernels_for(cfg).setup)
+    if (!spatial_kernels_for(cfg).found())
         return api_fail(-40, spatial_kernels_refusal(cfg));
+    if (cfg->model == FVB_MODEL_PLUGIN && !cfg->init_mvn)
+        return api_fail(-52, spatial_init_mvn_refusal);
     const int P = cfg->n_params;
     const int n = P + noise_outputs(cfg), rows = n * (n + 1) / 2 + n + 1;
     StagedProblem staged;

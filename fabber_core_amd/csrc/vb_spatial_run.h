@@ -78,6 +78,10 @@ struct fvb_spatial_run
     fvb_spatial sp;
     fvb::SpatialEnv env;
     fvb::SpatialKernels k;
+    // a body of a model library (FVB_MODEL_PLUGIN): the launcher of its spatial entry. The three kernels of the family
+    // that evaluate the model - set-up and the second sweep in its two forms - are the library's then and k's slots for
+    // them are NULL; everything else in k is the engine's own for the parameter count
+    fvb_device_spatial_launch_fn library = nullptr;
     fvb::SpatialArgs sa;
     hipStream_t stream = nullptr;
     int V = 0, P = 0, owned_begin = 0, owned_end = 0;
@@ -148,6 +152,8 @@ struct fvb_spatial_run
     int sweep(int it);
     int sweep_levels(int it, long long lo, long long hi);
     int sweep_noise(int it);
+    // the one launch of a kernel that evaluates the model (which: FVB_SPATIAL_KERNEL_*; fn: the engine's own kernel for it)
+    int launch_model_kernel(int which, fvb::SpatialKernelFn fn, unsigned grid, size_t lds, hipStream_t on);
     int copy_means(int v_begin, int v_count, double *host_means, int32_t *host_status, bool to_device);
     int finish();
 };

@@ -99,6 +99,17 @@ def lib():
         L.fabber_vb_device_nlls_model_params.argtypes = [C.c_int32]
         L.fabber_nlls_kernel_name.restype = C.c_char_p
         L.fabber_nlls_kernel_name.argtypes = [cfgp]
+        L.fabber_vb_register_device_spatial_model.restype = C.c_int32
+        L.fabber_vb_register_device_spatial_model.argtypes = [C.POINTER(vbabi.FvbDeviceSpatialModel)]
+        L.fabber_vb_unregister_device_spatial_model.restype = C.c_int32
+        L.fabber_vb_unregister_device_spatial_model.argtypes = [C.c_char_p, C.c_int32]
+        L.fabber_vb_device_spatial_model_count.restype = C.c_int32
+        L.fabber_vb_device_spatial_model_name.restype = C.c_char_p
+        L.fabber_vb_device_spatial_model_name.argtypes = [C.c_int32]
+        L.fabber_vb_device_spatial_model_params.restype = C.c_int32
+        L.fabber_vb_device_spatial_model_params.argtypes = [C.c_int32]
+        L.fabber_vb_spatial_kernel_name.restype = C.c_char_p
+        L.fabber_vb_spatial_kernel_name.argtypes = [cfgp]
         if L.fabber_vb_abi_version() != vbabi.FVB_ABI_VERSION:
             raise HipEngineError("libfabber_vb_hip.so ABI version mismatch: rebuild")
         _LIB = L
@@ -181,6 +192,23 @@ def unregister_device_nlls_model(name, n_params):
     _check(lib().fabber_vb_unregister_device_nlls_model(name.encode(), n_params))
 
 
+def device_spatial_models():
+    """(name, parameter count) of the spatial-VB entries registered with the engine (include/fabber_device_spatial_model.h)."""
+    L = lib()
+    return [(L.fabber_vb_device_spatial_model_name(i).decode(), L.fabber_vb_device_spatial_model_params(i))
+            for i in range(L.fabber_vb_device_spatial_model_count())]
+
+
+def register_device_spatial_model(descriptor):
+    """fabber_vb_register_device_spatial_model with a vbabi.FvbDeviceSpatialModel (the caller keeps it alive); raises with
+    the engine's message when the registration is refused."""
+    _check(lib().fabber_vb_register_device_spatial_model(C.byref(descriptor)))
+
+
+def unregister_device_spatial_model(name, n_params):
+    _check(lib().fabber_vb_unregister_device_spatial_model(name.encode(), n_params))
+
+
 def kernel_name(holder):
     return lib().fabber_vb_kernel_name(C.byref(holder.cfg)).decode()
 
@@ -189,6 +217,12 @@ def nlls_kernel_name(holder):
     """The kernel nlls_run_host would take: "nlls<exp,2>", "nlls<NAME,P>", "nlls_wave", "nlls_wave<NAME>", or "" where the
     run would be refused (a model without a device body, a library body without an NLLS entry)."""
     return lib().fabber_nlls_kernel_name(C.byref(holder.cfg)).decode()
+
+
+def spatial_kernel_name(holder):
+    """The kernel table run_spatial_host would take: "spatial<exp,2>", "spatial<NAME,P>", ..., or "" where the run would
+    answer -40 or -44 (no kernels for the model / parameter count / noise model, a library body without a spatial entry)."""
+    return lib().fabber_vb_spatial_kernel_name(C.byref(holder.cfg)).decode()
 
 
 def set_variant(variant):

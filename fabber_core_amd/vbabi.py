@@ -107,6 +107,14 @@ class FvbDeviceNllsModel(C.Structure):
                 ("n_params", C.c_int32), ("launch", LAUNCH_FN)]
 
 
+class FvbDeviceSpatialModel(C.Structure):
+    """fvb_device_spatial_model: the spatial VB kernels of a device body for one parameter count
+    (include/fabber_device_spatial_model.h)"""
+    LAUNCH_FN = C.CFUNCTYPE(C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32)
+    _fields_ = [("name", C.c_char_p), ("abi_version", C.c_int32), ("spatial_args_size", C.c_uint32), ("n_params", C.c_int32),
+                ("state_rows", C.c_int32), ("launch", LAUNCH_FN)]
+
+
 class FvbOutputs(C.Structure):
     _fields_ = [
         ("mvn", C.c_void_p),

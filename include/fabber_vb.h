@@ -572,6 +572,50 @@ int32_t fabber_vb_device_nlls_model_params(int32_t i);   /* -1 when i is out of 
  * library body without an NLLS entry). Reads n_voxels, n_times, n_params, model and device_model. */
 const char *fabber_nlls_kernel_name(const fvb_config *cfg);
 
+/*
+ * The spatial VB kernels for a device body of a model library (FABBER_DEVICE_SPATIAL_MODEL in
+ * include/fabber_device_spatial_model.h): a fourth, independent registry keyed by (name, n_params), 1 <= n_params <= 6.
+ * Of the spatial family only the set-up kernel and the second sweep evaluate the model; the library compiles those
+ * around its body and the engine keeps everything else (a_K, the first sweep in both forms, pack). With an entry next to
+ * a body of the same name in the registry of fabber_vb_register_device_model, fabber_vb_run_spatial_host / _device and
+ * fabber_vb_spatial_open accept FVB_MODEL_PLUGIN for that name and parameter count under white noise with one precision
+ * (-40 otherwise, as before; -52 without cfg->init_mvn: the kernels know no library's InitVoxelPosterior). `launch`
+ * receives which kernel to start (FVB_SPATIAL_KERNEL_*), need_f, the engine's arguments (fvb::SpatialArgs, sizeof =
+ * spatial_args_size), the grid size in 64-lane workgroups and the dynamic LDS bytes as the engine worked them out; it
+ * launches asynchronously on `stream` (a hipStream_t) and returns 0 or a negative code with its message in err.
+ * state_rows is the number of rows of the state image the kernels were compiled for (fvb::SpLayout<P>::ROWS).
+ * Registration is refused with -75 (descriptor, name or launcher NULL, name too long, n_params outside 1 ... 6), -76
+ * (another ABI version), -77 (another sizeof(fvb::SpatialArgs)) or -78 (duplicate entry); unregistering an entry that
+ * does not exist answers -79. The lifetime rules are those of fabber_vb_register_device_model.
+ */
+enum
+{
+    FVB_SPATIAL_KERNEL_SETUP = 0,      /* Vb::SetupPerVoxelDists */
+    FVB_SPATIAL_KERNEL_NOISE = 1,      /* the second sweep after per-level launches of the first */
+    FVB_SPATIAL_KERNEL_NOISE_SPLIT = 2 /* the second sweep of the split form: it completes the first sweep's update too */
+};
+typedef int32_t (*fvb_device_spatial_launch_fn)(int32_t which, int32_t need_f, const void *spatial_args, uint32_t grid,
+                                                uint32_t lds_bytes, void *stream, char *err, int32_t err_len);
+typedef struct fvb_device_spatial_model
+{
+    const char *name;
+    int32_t abi_version;        /* FVB_ABI_VERSION the library was compiled against */
+    uint32_t spatial_args_size; /* sizeof(fvb::SpatialArgs) */
+    int32_t n_params;
+    int32_t state_rows;         /* fvb::SpLayout<n_params>::ROWS */
+    fvb_device_spatial_launch_fn launch;
+} fvb_device_spatial_model;
+int32_t fabber_vb_register_device_spatial_model(const fvb_device_spatial_model *model);
+int32_t fabber_vb_unregister_device_spatial_model(const char *name, int32_t n_params);
+int32_t fabber_vb_device_spatial_model_count(void);
+const char *fabber_vb_device_spatial_model_name(int32_t i); /* NULL when i is out of range */
+int32_t fabber_vb_device_spatial_model_params(int32_t i);   /* 0 when i is out of range */
+
+/* Which kernel table fabber_vb_run_spatial_* would take for a configuration: "spatial<exp,2>" / "spatial<NAME,P>" ..., ""
+ * where the run would answer -40 or -44 (no kernels for the model / parameter count / noise model; a library body
+ * without a spatial entry). Reads n_params, n_phis, noise, ar_cross_terms, need_f, model and device_model. */
+const char *fabber_vb_spatial_kernel_name(const fvb_config *cfg);
+
 /* The engine's work buffers (the re-laid series, the spatial run's state) come from the current device's
  * stream-ordered memory pool, which keeps them between runs (a caller that fits volume after volume allocates
  * once). This returns what the pool holds to the driver; the reference has no counterpart (host memory, freed by
