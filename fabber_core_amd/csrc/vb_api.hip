@@ -7,6 +7,7 @@
  */
 #include "vb_lane_launch.h"
 #include "vb_host_stage.h"
+#include "vb_device_registry.h"
 #include "vb_wave_kernel.h"
 
 #include <hip/hip_runtime.h>
@@ -25,6 +26,55 @@
 
 using namespace fvb;
 
+namespace fvb
+{
+// Device bodies that model libraries have registered (include/fabber_device_model.h), by name ...
+template <> struct DeviceRegistryTraits<fvb_device_model>
+{
+    static constexpr const char *noun = "device model", *is = "is";
+    static constexpr int first_code = -70;
+    static std::vector<DeviceStructSize> sizes(const fvb_device_model &m)
+    {
+        return { { "KernelArgs", m.kernel_args_size, sizeof(KernelArgs) }, { "WaveLayout", m.wave_layout_size, sizeof(WaveLayout) } };
+    }
+    static const char *bad_params(const fvb_device_model &)
+    {
+        return nullptr;
+    }
+    static std::string entry(const std::string &name, int)
+    {
+        return "a device model named '" + name + "'";
+    }
+    static std::string absent(const std::string &name, int)
+    {
+        return "no device model '" + name + "' is registered";
+    }
+};
+// ... and the lane-per-voxel kernels of such bodies (include/fabber_device_lane_model.h), by (name, parameter count):
+// looked into only for a name the registry above holds.
+template <> struct DeviceRegistryTraits<fvb_device_lane_model>
+{
+    static constexpr const char *noun = "device lane model", *is = "are";
+    static constexpr int first_code = -70;
+    static std::vector<DeviceStructSize> sizes(const fvb_device_lane_model &m)
+    {
+        return { { "KernelArgs", m.kernel_args_size, sizeof(KernelArgs) } };
+    }
+    static const char *bad_params(const fvb_device_lane_model &m)
+    {
+        return (m.n_params < 1 || m.n_params > 6 || m.save_rows < 0) ? "the lane kernels of a library body exist for 1 to 6" : nullptr;
+    }
+    static std::string entry(const std::string &name, int n_params)
+    {
+        return "lane kernels of a device model named '" + name + "' with " + std::to_string(n_params) + " parameters";
+    }
+    static std::string absent(const std::string &name, int n_params)
+    {
+        return "no lane kernels of a device model '" + name + "' with " + std::to_string(n_params) + " parameters are registered";
+    }
+};
+} // namespace fvb
+
 namespace
 {
 thread_local std::string g_last_error;
@@ -41,65 +91,6 @@ int fail(int code, const std::string &msg)
     return code;
 }
 
-// Device bodies that model libraries have registered (include/fabber_device_model.h). The descriptors are the
-// libraries' own static objects: they stay valid until the library unregisters them (the destructor of the object that
-// registered them does).
-struct DeviceModelRegistry
-{
-    std::mutex lock;
-    std::vector<const fvb_device_model *> models;
-};
-DeviceModelRegistry &device_models()
-{
-    static DeviceModelRegistry *r = new DeviceModelRegistry; // (never destroyed: libraries unregister from static destructors)
-    return *r;
-}
-// (the name as a configuration carries it: not necessarily terminated)
-std::string config_device_model(const fvb_config *cfg)
-{
-    return std::string(cfg->device_model, strnlen(cfg->device_model, sizeof(cfg->device_model)));
-}
-// launch (optional): the body's launcher, copied while the registry is locked - a descriptor may be unregistered by
-// another thread at any time; the library itself must stay loaded while a run that uses its body is under way
-bool find_device_model(const std::string &name, fvb_device_model_launch_fn *launch = nullptr)
-{
-    DeviceModelRegistry &r = device_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    for (const fvb_device_model *m : r.models)
-        if (name == m->name)
-        {
-            if (launch)
-                *launch = m->launch;
-            return true;
-        }
-    return false;
-}
-// The lane-per-voxel kernels of such bodies (include/fabber_device_lane_model.h), by (name, parameter count): a
-// registry of its own, looked into only for a name the one above holds.
-struct DeviceLaneModelRegistry
-{
-    std::mutex lock;
-    std::vector<const fvb_device_lane_model *> models;
-};
-DeviceLaneModelRegistry &device_lane_models()
-{
-    static DeviceLaneModelRegistry *r = new DeviceLaneModelRegistry; // (never destroyed, as above)
-    return *r;
-}
-// (copies what a run needs while the registry is locked, as find_device_model does)
-bool find_device_lane_model(const std::string &name, int n_params, fvb_device_lane_launch_fn *launch, int *save_rows)
-{
-    DeviceLaneModelRegistry &r = device_lane_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    for (const fvb_device_lane_model *m : r.models)
-        if (m->n_params == n_params && name == m->name)
-        {
-            *launch = m->launch;
-            *save_rows = m->save_rows;
-            return true;
-        }
-    return false;
-}
 thread_local std::string g_kernel_name; // fabber_vb_kernel_name of a registered body: "wave<NAME>", "lane<NAME,P>"
 
 int validate(const fvb_config *cfg, bool allow_spatial = false, bool allow_no_noise = false)
@@ -144,15 +135,8 @@ int validate(const fvb_config *cfg, bool allow_spatial = false, bool allow_no_no
     if (cfg->model == FVB_MODEL_POLY && (cfg->n_params != cfg->model_iopt[0] + 1))
         return fail(-12, "poly model: n_params != degree + 1");
     if (cfg->model == FVB_MODEL_PLUGIN)
-    {
-        const std::string name = config_device_model(cfg);
-        if (name.empty())
-            return fail(-16, "FVB_MODEL_PLUGIN needs the name of a registered device model (fvb_config.device_model)");
-        if (!find_device_model(name))
-            return fail(-16, "no device model '" + name + "' is registered (fabber_vb_register_device_model)");
-        if (cfg->n_model_consts < 0 || (cfg->n_model_consts > 0 && !cfg->model_consts))
-            return fail(-17, "device model '" + name + "': n_model_consts constants announced but model_consts is NULL");
-    }
+        if (int rc = check_device_model_config(cfg))
+            return rc;
     for (int k = 0; k < cfg->n_params; k++)
     {
         // (validate() sees the configuration as the caller built it: with device entry points the table itself is device
@@ -285,9 +269,12 @@ LaneRoute select_lane(const fvb_config *cfg)
     if (g_variant == 2 || cfg->noise != FVB_NOISE_WHITE || cfg->n_phis != 1
         || !lane_worth_it(cfg, (double)cfg->n_times * (2 * cfg->n_params + 1)))
         return route;
-    int save_rows = 0;
-    if (find_device_lane_model(config_device_model(cfg), cfg->n_params, &route.launch, &save_rows))
-        route.k.save_rows = save_rows;
+    fvb_device_lane_model entry;
+    if (DeviceRegistry<fvb_device_lane_model>::instance().find(config_device_model(cfg), cfg->n_params, &entry))
+    {
+        route.launch = entry.launch;
+        route.k.save_rows = entry.save_rows;
+    }
     return route;
 }
 
@@ -651,116 +638,47 @@ void fabber_vb_set_residual_tolerance(double tol)
 
 int32_t fabber_vb_register_device_model(const fvb_device_model *model)
 {
-    if (!model || !model->name || !model->name[0] || !model->launch)
-        return fail(-70, "fabber_vb_register_device_model: descriptor, name or launcher is NULL");
-    const std::string name = model->name;
-    if (name.size() >= FVB_DEVICE_MODEL_NAME_MAX)
-        return fail(-70, "device model '" + name + "': the name is longer than " + std::to_string(FVB_DEVICE_MODEL_NAME_MAX - 1) + " characters");
-    if (model->abi_version != FVB_ABI_VERSION)
-        return fail(-71, "device model '" + name + "' was built for ABI version " + std::to_string(model->abi_version) + ", the engine is version "
-                + std::to_string(FVB_ABI_VERSION));
-    if (model->kernel_args_size != sizeof(KernelArgs) || model->wave_layout_size != sizeof(WaveLayout))
-        return fail(-72, "device model '" + name + "': struct size mismatch (KernelArgs " + std::to_string(model->kernel_args_size) + " against "
-                + std::to_string(sizeof(KernelArgs)) + " bytes, WaveLayout " + std::to_string(model->wave_layout_size) + " against "
-                + std::to_string(sizeof(WaveLayout)) + "): the library was compiled against other kernel headers");
-    DeviceModelRegistry &r = device_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    for (const fvb_device_model *m : r.models)
-        if (name == m->name)
-            return fail(-73, "a device model named '" + name + "' is already registered");
-    r.models.push_back(model);
-    return 0;
+    return DeviceRegistry<fvb_device_model>::instance().add(model);
 }
 
 int32_t fabber_vb_unregister_device_model(const char *name)
 {
-    if (!name)
-        return fail(-70, "fabber_vb_unregister_device_model: name is NULL");
-    DeviceModelRegistry &r = device_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    for (size_t i = 0; i < r.models.size(); i++)
-        if (strcmp(r.models[i]->name, name) == 0)
-        {
-            r.models.erase(r.models.begin() + (long)i);
-            return 0;
-        }
-    return fail(-74, std::string("no device model '") + name + "' is registered");
+    return DeviceRegistry<fvb_device_model>::instance().remove(name, 0);
 }
 
 int32_t fabber_vb_device_model_count(void)
 {
-    DeviceModelRegistry &r = device_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    return (int32_t)r.models.size();
+    return DeviceRegistry<fvb_device_model>::instance().count();
 }
 
 const char *fabber_vb_device_model_name(int32_t i)
 {
-    DeviceModelRegistry &r = device_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->name : nullptr;
+    return DeviceRegistry<fvb_device_model>::instance().name(i);
 }
 
 int32_t fabber_vb_register_device_lane_model(const fvb_device_lane_model *model)
 {
-    if (!model || !model->name || !model->name[0] || !model->launch)
-        return fail(-70, "fabber_vb_register_device_lane_model: descriptor, name or launcher is NULL");
-    const std::string name = model->name;
-    if (name.size() >= FVB_DEVICE_MODEL_NAME_MAX)
-        return fail(-70, "device lane model '" + name + "': the name is longer than " + std::to_string(FVB_DEVICE_MODEL_NAME_MAX - 1) + " characters");
-    if (model->abi_version != FVB_ABI_VERSION)
-        return fail(-71, "device lane model '" + name + "' was built for ABI version " + std::to_string(model->abi_version) + ", the engine is version "
-                + std::to_string(FVB_ABI_VERSION));
-    if (model->kernel_args_size != sizeof(KernelArgs))
-        return fail(-72, "device lane model '" + name + "': struct size mismatch (KernelArgs " + std::to_string(model->kernel_args_size) + " against "
-                + std::to_string(sizeof(KernelArgs)) + " bytes): the library was compiled against other kernel headers");
-    if (model->n_params < 1 || model->n_params > 6 || model->save_rows < 0)
-        return fail(-70, "device lane model '" + name + "': " + std::to_string(model->n_params)
-                + " parameters (the lane kernels of a library body exist for 1 to 6)");
-    DeviceLaneModelRegistry &r = device_lane_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    for (const fvb_device_lane_model *m : r.models)
-        if (m->n_params == model->n_params && name == m->name)
-            return fail(-73, "lane kernels of a device model named '" + name + "' with " + std::to_string(model->n_params)
-                    + " parameters are already registered");
-    r.models.push_back(model);
-    return 0;
+    return DeviceRegistry<fvb_device_lane_model>::instance().add(model);
 }
 
 int32_t fabber_vb_unregister_device_lane_model(const char *name, int32_t n_params)
 {
-    if (!name)
-        return fail(-70, "fabber_vb_unregister_device_lane_model: name is NULL");
-    DeviceLaneModelRegistry &r = device_lane_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    for (size_t i = 0; i < r.models.size(); i++)
-        if (r.models[i]->n_params == n_params && strcmp(r.models[i]->name, name) == 0)
-        {
-            r.models.erase(r.models.begin() + (long)i);
-            return 0;
-        }
-    return fail(-74, std::string("no lane kernels of a device model '") + name + "' with " + std::to_string(n_params) + " parameters are registered");
+    return DeviceRegistry<fvb_device_lane_model>::instance().remove(name, n_params);
 }
 
 int32_t fabber_vb_device_lane_model_count(void)
 {
-    DeviceLaneModelRegistry &r = device_lane_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    return (int32_t)r.models.size();
+    return DeviceRegistry<fvb_device_lane_model>::instance().count();
 }
 
 const char *fabber_vb_device_lane_model_name(int32_t i)
 {
-    DeviceLaneModelRegistry &r = device_lane_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->name : nullptr;
+    return DeviceRegistry<fvb_device_lane_model>::instance().name(i);
 }
 
 int32_t fabber_vb_device_lane_model_params(int32_t i)
 {
-    DeviceLaneModelRegistry &r = device_lane_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->n_params : 0;
+    return DeviceRegistry<fvb_device_lane_model>::instance().params(i, 0);
 }
 
 const char *fabber_vb_kernel_name(const fvb_config *cfg)
@@ -886,12 +804,12 @@ int run_device_as(const fvb_config *cfg, const void *data, const fvb_outputs *ou
     }
     if (cfg->model == FVB_MODEL_PLUGIN) // the kernels live in the library's code object: its launcher starts them
     {
-        fvb_device_model_launch_fn launch = nullptr;
-        if (!find_device_model(config_device_model(cfg), &launch))
+        fvb_device_model body;
+        if (!find_wave_body(config_device_model(cfg), &body))
             return fail(-16, "no device model '" + config_device_model(cfg) + "' is registered (fabber_vb_register_device_model)");
         char msg[512];
         msg[0] = 0;
-        rc = launch(&ka, (void *)stream, msg, (int32_t)sizeof(msg));
+        rc = body.launch(&ka, (void *)stream, msg, (int32_t)sizeof(msg));
         return rc ? fail(rc, msg) : 0;
     }
     return launch_wave_kernel(ka, stream, g_last_error);

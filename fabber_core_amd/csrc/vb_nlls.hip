@@ -5,10 +5,8 @@
  */
 #include "vb_nlls_launch.h"
 
-#include "vb_host_stage.h"
+#include "vb_device_registry.h"
 
-#include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -57,52 +55,35 @@ NllsKernelInfo get_nlls_kernel(int model, int P)
     }
     return NllsKernelInfo{ nullptr, nullptr };
 }
+
+// The NLLS minimisers of device bodies that model libraries have registered (include/fabber_device_nlls_model.h), by
+// (name, parameter count; 0 = the wave-per-voxel minimiser).
+template <> struct DeviceRegistryTraits<fvb_device_nlls_model>
+{
+    static constexpr const char *noun = "device NLLS model", *is = "is";
+    static constexpr int first_code = -70;
+    static std::vector<DeviceStructSize> sizes(const fvb_device_nlls_model &m)
+    {
+        return { { "NllsArgs", m.nlls_args_size, sizeof(NllsArgs) }, { "WaveLayout", m.wave_layout_size, sizeof(WaveLayout) } };
+    }
+    static const char *bad_params(const fvb_device_nlls_model &m)
+    {
+        return (m.n_params < 0 || m.n_params > 6) ? "0 = the wave minimiser; the lane minimisers of a library body exist for 1 to 6" : nullptr;
+    }
+    static std::string entry(const std::string &name, int n_params)
+    {
+        return n_params == 0 ? "the wave NLLS minimiser of a device model named '" + name + "'"
+                             : "the lane NLLS minimiser of a device model named '" + name + "' with " + std::to_string(n_params) + " parameters";
+    }
+    static std::string absent(const std::string &name, int n_params)
+    {
+        return entry(name, n_params) + " is not registered";
+    }
+};
 } // namespace fvb
 
 namespace
 {
-// The NLLS minimisers of device bodies that model libraries have registered (include/fabber_device_nlls_model.h), by
-// (name, parameter count; 0 = the wave-per-voxel minimiser). The descriptors are the libraries' own static objects, as in
-// the registries of vb_api.hip.
-struct DeviceNllsModelRegistry
-{
-    std::mutex lock;
-    std::vector<const fvb_device_nlls_model *> models;
-};
-DeviceNllsModelRegistry &device_nlls_models()
-{
-    static DeviceNllsModelRegistry *r = new DeviceNllsModelRegistry; // (never destroyed: libraries unregister from static destructors)
-    return *r;
-}
-// (copies the launcher while the registry is locked: a descriptor may be unregistered by another thread at any time)
-bool find_device_nlls_model(const std::string &name, int n_params, fvb_device_nlls_launch_fn *launch)
-{
-    DeviceNllsModelRegistry &r = device_nlls_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    for (const fvb_device_nlls_model *m : r.models)
-        if (m->n_params == n_params && name == m->name)
-        {
-            *launch = m->launch;
-            return true;
-        }
-    return false;
-}
-std::string entry_text(const std::string &name, int n_params)
-{
-    return n_params == 0 ? "the wave NLLS minimiser of a device model named '" + name + "'"
-                         : "the lane NLLS minimiser of a device model named '" + name + "' with " + std::to_string(n_params) + " parameters";
-}
-bool device_model_registered(const std::string &name)
-{
-    for (int i = 0; i < fabber_vb_device_model_count(); i++)
-    {
-        const char *n = fabber_vb_device_model_name(i);
-        if (n && name == n)
-            return true;
-    }
-    return false;
-}
-
 // what a configuration runs on
 struct NllsRoute
 {
@@ -137,21 +118,18 @@ int select_nlls(const fvb_config *cfg, NllsRoute &route, const fvb_nlls *nl = nu
                             "series does not fit the 160 KB of LDS the wave-per-voxel kernel needs";
     if (cfg->model == FVB_MODEL_PLUGIN) // a body of a model library: with the NLLS entries its library registered
     {
-        const std::string name(cfg->device_model, strnlen(cfg->device_model, sizeof(cfg->device_model)));
-        if (name.empty())
-            return api_fail(-16, "FVB_MODEL_PLUGIN needs the name of a registered device model (fvb_config.device_model)");
-        if (!device_model_registered(name))
-            return api_fail(-16, "no device model '" + name + "' is registered (fabber_vb_register_device_model)");
-        if (cfg->n_model_consts < 0 || (cfg->n_model_consts > 0 && !cfg->model_consts))
-            return api_fail(-17, "device model '" + name + "': n_model_consts constants announced but model_consts is NULL");
-        fvb_device_nlls_launch_fn wave = nullptr, lane = nullptr;
-        if (!find_device_nlls_model(name, 0, &wave))
+        if (int rc = check_device_model_config(cfg))
+            return rc;
+        const std::string name = config_device_model(cfg);
+        DeviceRegistry<fvb_device_nlls_model> &entries = DeviceRegistry<fvb_device_nlls_model>::instance();
+        fvb_device_nlls_model wave, lane;
+        if (!entries.find(name, 0, &wave))
             return api_fail(-61, "method=nlls needs a forward model with a device body");
-        const bool has_lane = cfg->n_params <= 6 && !cfg->params_ext && find_device_nlls_model(name, cfg->n_params, &lane);
+        const bool has_lane = cfg->n_params <= 6 && !cfg->params_ext && entries.find(name, cfg->n_params, &lane);
         route.lane = nlls_takes_lane(has_lane, api_variant(), *cfg);
         if (!route.lane && !wave_fits)
             return api_fail(-61, no_kernel);
-        route.library = route.lane ? lane : wave;
+        route.library = route.lane ? lane.launch : wave.launch;
         route.name = route.lane ? "nlls<" + name + "," + std::to_string(cfg->n_params) + ">" : "nlls_wave<" + name + ">";
         return 0;
     }
@@ -188,64 +166,27 @@ void fabber_nlls_defaults(fvb_nlls *nl)
 
 int32_t fabber_vb_register_device_nlls_model(const fvb_device_nlls_model *model)
 {
-    if (!model || !model->name || !model->name[0] || !model->launch)
-        return api_fail(-70, "fabber_vb_register_device_nlls_model: descriptor, name or launcher is NULL");
-    const std::string name = model->name;
-    if (name.size() >= FVB_DEVICE_MODEL_NAME_MAX)
-        return api_fail(-70, "device NLLS model '" + name + "': the name is longer than " + std::to_string(FVB_DEVICE_MODEL_NAME_MAX - 1) + " characters");
-    if (model->abi_version != FVB_ABI_VERSION)
-        return api_fail(-71, "device NLLS model '" + name + "' was built for ABI version " + std::to_string(model->abi_version) + ", the engine is version "
-                + std::to_string(FVB_ABI_VERSION));
-    if (model->nlls_args_size != sizeof(NllsArgs) || model->wave_layout_size != sizeof(WaveLayout))
-        return api_fail(-72, "device NLLS model '" + name + "': struct size mismatch (NllsArgs " + std::to_string(model->nlls_args_size) + " against "
-                + std::to_string(sizeof(NllsArgs)) + " bytes, WaveLayout " + std::to_string(model->wave_layout_size) + " against "
-                + std::to_string(sizeof(WaveLayout)) + "): the library was compiled against other kernel headers");
-    if (model->n_params < 0 || model->n_params > 6)
-        return api_fail(-70, "device NLLS model '" + name + "': " + std::to_string(model->n_params)
-                + " parameters (0 = the wave minimiser; the lane minimisers of a library body exist for 1 to 6)");
-    DeviceNllsModelRegistry &r = device_nlls_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    for (const fvb_device_nlls_model *m : r.models)
-        if (m->n_params == model->n_params && name == m->name)
-            return api_fail(-73, entry_text(name, model->n_params) + " is already registered");
-    r.models.push_back(model);
-    return 0;
+    return DeviceRegistry<fvb_device_nlls_model>::instance().add(model);
 }
 
 int32_t fabber_vb_unregister_device_nlls_model(const char *name, int32_t n_params)
 {
-    if (!name)
-        return api_fail(-70, "fabber_vb_unregister_device_nlls_model: name is NULL");
-    DeviceNllsModelRegistry &r = device_nlls_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    for (size_t i = 0; i < r.models.size(); i++)
-        if (r.models[i]->n_params == n_params && strcmp(r.models[i]->name, name) == 0)
-        {
-            r.models.erase(r.models.begin() + (long)i);
-            return 0;
-        }
-    return api_fail(-74, entry_text(name, n_params) + " is not registered");
+    return DeviceRegistry<fvb_device_nlls_model>::instance().remove(name, n_params);
 }
 
 int32_t fabber_vb_device_nlls_model_count(void)
 {
-    DeviceNllsModelRegistry &r = device_nlls_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    return (int32_t)r.models.size();
+    return DeviceRegistry<fvb_device_nlls_model>::instance().count();
 }
 
 const char *fabber_vb_device_nlls_model_name(int32_t i)
 {
-    DeviceNllsModelRegistry &r = device_nlls_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->name : nullptr;
+    return DeviceRegistry<fvb_device_nlls_model>::instance().name(i);
 }
 
 int32_t fabber_vb_device_nlls_model_params(int32_t i)
 {
-    DeviceNllsModelRegistry &r = device_nlls_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->n_params : -1;
+    return DeviceRegistry<fvb_device_nlls_model>::instance().params(i, -1);
 }
 
 const char *fabber_nlls_kernel_name(const fvb_config *cfg)

@@ -5,6 +5,7 @@
  * device variants and vb_spatial_multi.hip for one volume on several devices.
  */
 #include "vb_spatial_geom.h"
+#include "vb_device_registry.h"
 
 #include <hip/hip_runtime.h>
 
@@ -33,48 +34,34 @@ int fvb::spatial_noise_kind(const fvb_config *cfg)
 }
 const char *const fvb::spatial_noise_refusal
     = "spatial VB runs white noise with up to 8 noise precisions and AR(1) noise with one or two echoes";
-namespace
+namespace fvb
 {
 // The spatial kernels of device bodies that model libraries have registered (include/fabber_device_spatial_model.h), by
-// (name, parameter count). The descriptors are the libraries' own static objects, as in the registries of vb_api.hip.
-struct DeviceSpatialModelRegistry
+// (name, parameter count).
+template <> struct DeviceRegistryTraits<fvb_device_spatial_model>
 {
-    std::mutex lock;
-    std::vector<const fvb_device_spatial_model *> models;
-};
-DeviceSpatialModelRegistry &device_spatial_models()
-{
-    static DeviceSpatialModelRegistry *r = new DeviceSpatialModelRegistry; // (never destroyed: libraries unregister from static destructors)
-    return *r;
-}
-// (copies what a run needs while the registry is locked: a descriptor may be unregistered by another thread at any time)
-bool find_device_spatial_model(const std::string &name, int n_params, fvb_device_spatial_launch_fn *launch, int *state_rows)
-{
-    DeviceSpatialModelRegistry &r = device_spatial_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    for (const fvb_device_spatial_model *m : r.models)
-        if (m->n_params == n_params && name == m->name)
-        {
-            *launch = m->launch;
-            *state_rows = m->state_rows;
-            return true;
-        }
-    return false;
-}
-bool device_model_registered(const std::string &name)
-{
-    for (int i = 0; i < fabber_vb_device_model_count(); i++)
+    static constexpr const char *noun = "device spatial model", *is = "are";
+    static constexpr int first_code = -75;
+    static std::vector<DeviceStructSize> sizes(const fvb_device_spatial_model &m)
     {
-        const char *n = fabber_vb_device_model_name(i);
-        if (n && name == n)
-            return true;
+        return { { "SpatialArgs", m.spatial_args_size, sizeof(SpatialArgs) } };
     }
-    return false;
-}
-std::string spatial_entry_text(const std::string &name, int n_params)
+    static const char *bad_params(const fvb_device_spatial_model &m)
+    {
+        return (m.n_params < 1 || m.n_params > 6) ? "the spatial kernels of a library body exist for 1 to 6" : nullptr;
+    }
+    static std::string entry(const std::string &name, int n_params)
+    {
+        return "spatial kernels of a device model named '" + name + "' with " + std::to_string(n_params) + " parameters";
+    }
+    static std::string absent(const std::string &name, int n_params)
+    {
+        return "no " + entry(name, n_params) + " are registered";
+    }
+};
+} // namespace fvb
+namespace
 {
-    return "spatial kernels of a device model named '" + name + "' with " + std::to_string(n_params) + " parameters";
-}
 
 // What a configuration runs on: the kernel table, and for a body of a model library the launcher of its entry
 struct SpatialRoute
@@ -97,20 +84,19 @@ thread_local std::string g_spatial_kernel_name;
 static SpatialRoute spatial_route_library(const fvb_config *cfg, int kind)
 {
     SpatialRoute route;
-    const std::string name(cfg->device_model, strnlen(cfg->device_model, sizeof(cfg->device_model)));
-    fvb_device_spatial_launch_fn launch = nullptr;
-    int state_rows = 0;
-    if (kind != FVB_SPNZ_WHITE || cfg->params_ext || name.empty() || !device_model_registered(name)
-        || !find_device_spatial_model(name, cfg->n_params, &launch, &state_rows))
+    const std::string name = config_device_model(cfg);
+    fvb_device_spatial_model entry;
+    if (kind != FVB_SPNZ_WHITE || cfg->params_ext || name.empty() || !find_wave_body(name)
+        || !DeviceRegistry<fvb_device_spatial_model>::instance().find(name, cfg->n_params, &entry))
         return route;
     SpatialKernels k = get_spatial_kernels_linear(cfg->n_params, cfg->need_f != 0);
-    if (!k.setup || k.wave || k.lds_classes || k.state_rows != state_rows) // (state_rows: compiled against another SpLayout)
+    if (!k.setup || k.wave || k.lds_classes || k.state_rows != entry.state_rows) // (state_rows: compiled against another SpLayout)
         return route;
     k.setup = k.noise = k.noise_fast = k.noise_acc = k.noise_fast_acc = nullptr; // the library's
     route.name = "spatial<" + name + "," + std::to_string(cfg->n_params) + ">";
     k.name = nullptr; // (route.name)
     route.k = k;
-    route.library = launch;
+    route.library = entry.launch;
     return route;
 }
 
@@ -892,63 +878,27 @@ extern "C" {
 
 int32_t fabber_vb_register_device_spatial_model(const fvb_device_spatial_model *model)
 {
-    if (!model || !model->name || !model->name[0] || !model->launch)
-        return api_fail(-75, "fabber_vb_register_device_spatial_model: descriptor, name or launcher is NULL");
-    const std::string name = model->name;
-    if (name.size() >= FVB_DEVICE_MODEL_NAME_MAX)
-        return api_fail(-75, "device spatial model '" + name + "': the name is longer than " + std::to_string(FVB_DEVICE_MODEL_NAME_MAX - 1) + " characters");
-    if (model->abi_version != FVB_ABI_VERSION)
-        return api_fail(-76, "device spatial model '" + name + "' was built for ABI version " + std::to_string(model->abi_version) + ", the engine is version "
-                + std::to_string(FVB_ABI_VERSION));
-    if (model->spatial_args_size != sizeof(SpatialArgs))
-        return api_fail(-77, "device spatial model '" + name + "': struct size mismatch (SpatialArgs " + std::to_string(model->spatial_args_size) + " against "
-                + std::to_string(sizeof(SpatialArgs)) + " bytes): the library was compiled against other kernel headers");
-    if (model->n_params < 1 || model->n_params > 6)
-        return api_fail(-75, "device spatial model '" + name + "': " + std::to_string(model->n_params)
-                + " parameters (the spatial kernels of a library body exist for 1 to 6)");
-    DeviceSpatialModelRegistry &r = device_spatial_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    for (const fvb_device_spatial_model *m : r.models)
-        if (m->n_params == model->n_params && name == m->name)
-            return api_fail(-78, spatial_entry_text(name, model->n_params) + " are already registered");
-    r.models.push_back(model);
-    return 0;
+    return DeviceRegistry<fvb_device_spatial_model>::instance().add(model);
 }
 
 int32_t fabber_vb_unregister_device_spatial_model(const char *name, int32_t n_params)
 {
-    if (!name)
-        return api_fail(-75, "fabber_vb_unregister_device_spatial_model: name is NULL");
-    DeviceSpatialModelRegistry &r = device_spatial_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    for (size_t i = 0; i < r.models.size(); i++)
-        if (r.models[i]->n_params == n_params && strcmp(r.models[i]->name, name) == 0)
-        {
-            r.models.erase(r.models.begin() + (long)i);
-            return 0;
-        }
-    return api_fail(-79, "no " + spatial_entry_text(name, n_params) + " are registered");
+    return DeviceRegistry<fvb_device_spatial_model>::instance().remove(name, n_params);
 }
 
 int32_t fabber_vb_device_spatial_model_count(void)
 {
-    DeviceSpatialModelRegistry &r = device_spatial_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    return (int32_t)r.models.size();
+    return DeviceRegistry<fvb_device_spatial_model>::instance().count();
 }
 
 const char *fabber_vb_device_spatial_model_name(int32_t i)
 {
-    DeviceSpatialModelRegistry &r = device_spatial_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->name : nullptr;
+    return DeviceRegistry<fvb_device_spatial_model>::instance().name(i);
 }
 
 int32_t fabber_vb_device_spatial_model_params(int32_t i)
 {
-    DeviceSpatialModelRegistry &r = device_spatial_models();
-    std::lock_guard<std::mutex> hold(r.lock);
-    return (i >= 0 && (size_t)i < r.models.size()) ? r.models[(size_t)i]->n_params : 0;
+    return DeviceRegistry<fvb_device_spatial_model>::instance().params(i, 0);
 }
 
 // (the selection function of the run: "" where open() would answer -40 or -44)

@@ -16,6 +16,14 @@ LIB_PATH = os.environ.get("FVB_LIB_PATH") or os.path.join(_HERE, "lib", "libfabb
 _LIB = None
 
 
+# The registries of what model libraries compile around their device bodies (fabber_vb.h): the kind as the C functions
+# spell it, the descriptor class, and whether an entry's key carries a parameter count next to the name
+_DEVICE_ENTRIES = (("device_model", vbabi.FvbDeviceModel, False),
+                   ("device_lane_model", vbabi.FvbDeviceLaneModel, True),
+                   ("device_nlls_model", vbabi.FvbDeviceNllsModel, True),
+                   ("device_spatial_model", vbabi.FvbDeviceSpatialModel, True))
+
+
 class HipEngineError(RuntimeError):
     pass
 
@@ -72,42 +80,21 @@ def lib():
         L.fabber_nlls_run_device.argtypes = [cfgp, C.POINTER(vbabi.FvbNlls), C.c_void_p, outp, C.c_void_p, C.c_int32]
         L.fabber_nlls_defaults.restype = None
         L.fabber_nlls_defaults.argtypes = [C.POINTER(vbabi.FvbNlls)]
-        L.fabber_vb_register_device_model.restype = C.c_int32
-        L.fabber_vb_register_device_model.argtypes = [C.POINTER(vbabi.FvbDeviceModel)]
-        L.fabber_vb_unregister_device_model.restype = C.c_int32
-        L.fabber_vb_unregister_device_model.argtypes = [C.c_char_p]
-        L.fabber_vb_device_model_count.restype = C.c_int32
-        L.fabber_vb_device_model_name.restype = C.c_char_p
-        L.fabber_vb_device_model_name.argtypes = [C.c_int32]
-        L.fabber_vb_register_device_lane_model.restype = C.c_int32
-        L.fabber_vb_register_device_lane_model.argtypes = [C.POINTER(vbabi.FvbDeviceLaneModel)]
-        L.fabber_vb_unregister_device_lane_model.restype = C.c_int32
-        L.fabber_vb_unregister_device_lane_model.argtypes = [C.c_char_p, C.c_int32]
-        L.fabber_vb_device_lane_model_count.restype = C.c_int32
-        L.fabber_vb_device_lane_model_name.restype = C.c_char_p
-        L.fabber_vb_device_lane_model_name.argtypes = [C.c_int32]
-        L.fabber_vb_device_lane_model_params.restype = C.c_int32
-        L.fabber_vb_device_lane_model_params.argtypes = [C.c_int32]
-        L.fabber_vb_register_device_nlls_model.restype = C.c_int32
-        L.fabber_vb_register_device_nlls_model.argtypes = [C.POINTER(vbabi.FvbDeviceNllsModel)]
-        L.fabber_vb_unregister_device_nlls_model.restype = C.c_int32
-        L.fabber_vb_unregister_device_nlls_model.argtypes = [C.c_char_p, C.c_int32]
-        L.fabber_vb_device_nlls_model_count.restype = C.c_int32
-        L.fabber_vb_device_nlls_model_name.restype = C.c_char_p
-        L.fabber_vb_device_nlls_model_name.argtypes = [C.c_int32]
-        L.fabber_vb_device_nlls_model_params.restype = C.c_int32
-        L.fabber_vb_device_nlls_model_params.argtypes = [C.c_int32]
+        for kind, descriptor, keyed in _DEVICE_ENTRIES:
+            def fn(what):
+                return getattr(L, "fabber_vb_" + what.replace("KIND", kind))
+            fn("register_KIND").restype = C.c_int32
+            fn("register_KIND").argtypes = [C.POINTER(descriptor)]
+            fn("unregister_KIND").restype = C.c_int32
+            fn("unregister_KIND").argtypes = [C.c_char_p] + [C.c_int32] * keyed
+            fn("KIND_count").restype = C.c_int32
+            fn("KIND_name").restype = C.c_char_p
+            fn("KIND_name").argtypes = [C.c_int32]
+            if keyed:
+                fn("KIND_params").restype = C.c_int32
+                fn("KIND_params").argtypes = [C.c_int32]
         L.fabber_nlls_kernel_name.restype = C.c_char_p
         L.fabber_nlls_kernel_name.argtypes = [cfgp]
-        L.fabber_vb_register_device_spatial_model.restype = C.c_int32
-        L.fabber_vb_register_device_spatial_model.argtypes = [C.POINTER(vbabi.FvbDeviceSpatialModel)]
-        L.fabber_vb_unregister_device_spatial_model.restype = C.c_int32
-        L.fabber_vb_unregister_device_spatial_model.argtypes = [C.c_char_p, C.c_int32]
-        L.fabber_vb_device_spatial_model_count.restype = C.c_int32
-        L.fabber_vb_device_spatial_model_name.restype = C.c_char_p
-        L.fabber_vb_device_spatial_model_name.argtypes = [C.c_int32]
-        L.fabber_vb_device_spatial_model_params.restype = C.c_int32
-        L.fabber_vb_device_spatial_model_params.argtypes = [C.c_int32]
         L.fabber_vb_spatial_kernel_name.restype = C.c_char_p
         L.fabber_vb_spatial_kernel_name.argtypes = [cfgp]
         if L.fabber_vb_abi_version() != vbabi.FVB_ABI_VERSION:
@@ -141,72 +128,73 @@ def load_model_library(path):
     return _MODEL_LIBRARIES[path]
 
 
+def _listed(kind, keyed):
+    L = lib()
+    names = [getattr(L, "fabber_vb_%s_name" % kind)(i).decode() for i in range(getattr(L, "fabber_vb_%s_count" % kind)())]
+    return [(n, getattr(L, "fabber_vb_%s_params" % kind)(i)) for i, n in enumerate(names)] if keyed else names
+
+
+def _register(kind, descriptor):
+    _check(getattr(lib(), "fabber_vb_register_" + kind)(C.byref(descriptor)))
+
+
+def _unregister(kind, name, *n_params):
+    _check(getattr(lib(), "fabber_vb_unregister_" + kind)(name.encode(), *n_params))
+
+
 def device_models():
     """Names of the device bodies registered with the engine."""
-    L = lib()
-    return [L.fabber_vb_device_model_name(i).decode() for i in range(L.fabber_vb_device_model_count())]
+    return _listed("device_model", False)
 
 
 def register_device_model(descriptor):
     """fabber_vb_register_device_model with a vbabi.FvbDeviceModel (the caller keeps it alive); raises with the engine's
-    message when the registration is refused."""
-    _check(lib().fabber_vb_register_device_model(C.byref(descriptor)))
+    message when the registration is refused. The three below: the same with the descriptor class of their kind."""
+    _register("device_model", descriptor)
 
 
 def unregister_device_model(name):
-    _check(lib().fabber_vb_unregister_device_model(name.encode()))
+    _unregister("device_model", name)
 
 
 def device_lane_models():
     """(name, parameter count) of the lane-kernel entries registered with the engine (include/fabber_device_lane_model.h)."""
-    L = lib()
-    return [(L.fabber_vb_device_lane_model_name(i).decode(), L.fabber_vb_device_lane_model_params(i))
-            for i in range(L.fabber_vb_device_lane_model_count())]
+    return _listed("device_lane_model", True)
 
 
 def register_device_lane_model(descriptor):
-    """fabber_vb_register_device_lane_model with a vbabi.FvbDeviceLaneModel (the caller keeps it alive); raises with the
-    engine's message when the registration is refused."""
-    _check(lib().fabber_vb_register_device_lane_model(C.byref(descriptor)))
+    _register("device_lane_model", descriptor)
 
 
 def unregister_device_lane_model(name, n_params):
-    _check(lib().fabber_vb_unregister_device_lane_model(name.encode(), n_params))
+    _unregister("device_lane_model", name, n_params)
 
 
 def device_nlls_models():
     """(name, parameter count) of the NLLS minimisers registered with the engine (include/fabber_device_nlls_model.h);
     a count of 0 is the wave-per-voxel minimiser."""
-    L = lib()
-    return [(L.fabber_vb_device_nlls_model_name(i).decode(), L.fabber_vb_device_nlls_model_params(i))
-            for i in range(L.fabber_vb_device_nlls_model_count())]
+    return _listed("device_nlls_model", True)
 
 
 def register_device_nlls_model(descriptor):
-    """fabber_vb_register_device_nlls_model with a vbabi.FvbDeviceNllsModel (the caller keeps it alive); raises with the
-    engine's message when the registration is refused."""
-    _check(lib().fabber_vb_register_device_nlls_model(C.byref(descriptor)))
+    _register("device_nlls_model", descriptor)
 
 
 def unregister_device_nlls_model(name, n_params):
-    _check(lib().fabber_vb_unregister_device_nlls_model(name.encode(), n_params))
+    _unregister("device_nlls_model", name, n_params)
 
 
 def device_spatial_models():
     """(name, parameter count) of the spatial-VB entries registered with the engine (include/fabber_device_spatial_model.h)."""
-    L = lib()
-    return [(L.fabber_vb_device_spatial_model_name(i).decode(), L.fabber_vb_device_spatial_model_params(i))
-            for i in range(L.fabber_vb_device_spatial_model_count())]
+    return _listed("device_spatial_model", True)
 
 
 def register_device_spatial_model(descriptor):
-    """fabber_vb_register_device_spatial_model with a vbabi.FvbDeviceSpatialModel (the caller keeps it alive); raises with
-    the engine's message when the registration is refused."""
-    _check(lib().fabber_vb_register_device_spatial_model(C.byref(descriptor)))
+    _register("device_spatial_model", descriptor)
 
 
 def unregister_device_spatial_model(name, n_params):
-    _check(lib().fabber_vb_unregister_device_spatial_model(name.encode(), n_params))
+    _unregister("device_spatial_model", name, n_params)
 
 
 def kernel_name(holder):

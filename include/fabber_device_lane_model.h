@@ -42,12 +42,8 @@
 #ifndef FABBER_DEVICE_LANE_MODEL_H
 #define FABBER_DEVICE_LANE_MODEL_H
 
-#include "fabber_vb.h"
+#include "fabber_device_registration.h"
 #include "../fabber_core_amd/csrc/vb_lane_launch.h"
-
-#include <cstdio>
-#include <cstring>
-#include <string>
 
 namespace fvb
 {
@@ -81,48 +77,14 @@ inline int32_t device_lane_model_launch(LaneKernelsFn kernels, const void *kerne
     const KernelArgs &ka = *static_cast<const KernelArgs *>(kernel_args);
     std::string msg;
     const int rc = launch_lane_kernel(kernels(ka.cfg.need_f != 0), ka, feed, counting != 0, 0, static_cast<hipStream_t>(stream), msg);
-    if (rc && err && err_len > 0)
-    {
-        strncpy(err, msg.c_str(), (size_t)err_len - 1);
-        err[err_len - 1] = 0;
-    }
-    return rc;
+    return device_launch_result(rc, msg, err, err_len);
 }
-
-// registers in its constructor, unregisters in its destructor (the library's static object)
-struct DeviceLaneModelRegistration
-{
-    fvb_device_lane_model descriptor;
-    bool registered;
-    DeviceLaneModelRegistration(const char *name, int n_params, int save_rows, fvb_device_lane_launch_fn launch)
-    {
-        descriptor.name = name;
-        descriptor.abi_version = FVB_ABI_VERSION;
-        descriptor.kernel_args_size = (uint32_t)sizeof(KernelArgs);
-        descriptor.n_params = n_params;
-        descriptor.save_rows = save_rows;
-        descriptor.launch = launch;
-        registered = fabber_vb_register_device_lane_model(&descriptor) == 0;
-        if (!registered)
-            fprintf(stderr, "fabber: lane kernels of device model '%s' (%d parameters) not registered (%s): the model runs on the wave kernels\n",
-                name, n_params, fabber_vb_last_error());
-    }
-    ~DeviceLaneModelRegistration()
-    {
-        if (registered)
-            (void)fabber_vb_unregister_device_lane_model(descriptor.name, descriptor.n_params);
-    }
-    DeviceLaneModelRegistration(const DeviceLaneModelRegistration &) = delete;
-    DeviceLaneModelRegistration &operator=(const DeviceLaneModelRegistration &) = delete;
-};
 } // namespace fvb
 
-#define FABBER_DEVICE_LANE_MODEL_CAT2(a, b) a##b
-#define FABBER_DEVICE_LANE_MODEL_CAT(a, b) FABBER_DEVICE_LANE_MODEL_CAT2(a, b)
 // (FVB_LANE_CASE is the engine's own table entry of a built-in model: the same eight kernels, the same names)
 #define FABBER_DEVICE_LANE_MODEL(NAME, EVAL, NPARAMS)                                                                        \
     static_assert((NPARAMS) >= 1 && (NPARAMS) <= 6, "FABBER_DEVICE_LANE_MODEL: the lane kernels of a library body exist for 1 to 6 parameters"); \
-    static fvb::LaneKernelInfo FABBER_DEVICE_LANE_MODEL_CAT(fabber_device_lane_kernels_, __LINE__)(bool need_f)              \
+    static fvb::LaneKernelInfo FABBER_DEVICE_CAT(fabber_device_lane_kernels_, __LINE__)(bool need_f)              \
     {                                                                                                                        \
         using namespace fvb;                                                                                                 \
         switch (NPARAMS)                                                                                                     \
@@ -131,13 +93,16 @@ struct DeviceLaneModelRegistration
         }                                                                                                                    \
         return LaneKernelInfo{ nullptr, 0, nullptr };                                                                        \
     }                                                                                                                        \
-    static int32_t FABBER_DEVICE_LANE_MODEL_CAT(fabber_device_lane_launch_, __LINE__)(                                       \
+    static int32_t FABBER_DEVICE_CAT(fabber_device_lane_launch_, __LINE__)(                                       \
         const void *kernel_args, int32_t feed, int32_t counting, void *stream, char *err, int32_t err_len)                   \
     {                                                                                                                        \
-        return fvb::device_lane_model_launch(&FABBER_DEVICE_LANE_MODEL_CAT(fabber_device_lane_kernels_, __LINE__), kernel_args, feed, \
+        return fvb::device_lane_model_launch(&FABBER_DEVICE_CAT(fabber_device_lane_kernels_, __LINE__), kernel_args, feed, \
             counting, stream, err, err_len);                                                                                 \
     }                                                                                                                        \
-    static fvb::DeviceLaneModelRegistration FABBER_DEVICE_LANE_MODEL_CAT(fabber_device_lane_registration_, __LINE__)(        \
-        NAME, NPARAMS, fvb::lane_save_rows<NPARAMS>(), &FABBER_DEVICE_LANE_MODEL_CAT(fabber_device_lane_launch_, __LINE__));
+    static fvb::DeviceRegistration<fvb_device_lane_model> FABBER_DEVICE_CAT(fabber_device_lane_registration_, __LINE__)(      \
+        fvb_device_lane_model{ NAME, FVB_ABI_VERSION, (uint32_t)sizeof(fvb::KernelArgs), NPARAMS, fvb::lane_save_rows<NPARAMS>(), \
+            &FABBER_DEVICE_CAT(fabber_device_lane_launch_, __LINE__) },                                                      \
+        NPARAMS, &fabber_vb_register_device_lane_model, &fabber_vb_unregister_device_lane_model, "lane kernels of ",         \
+        "the model runs on the wave kernels");
 
 #endif /* FABBER_DEVICE_LANE_MODEL_H */

@@ -54,12 +54,8 @@
 #ifndef FABBER_DEVICE_MODEL_H
 #define FABBER_DEVICE_MODEL_H
 
-#include "fabber_vb.h"
+#include "fabber_device_registration.h"
 #include "../fabber_core_amd/csrc/vb_wave_launch.h"
-
-#include <cstdio>
-#include <cstring>
-#include <string>
 
 namespace fvb
 {
@@ -69,44 +65,20 @@ int32_t device_model_launch(const void *kernel_args, void *stream, char *err, in
     static const WaveKernelSet set = wave_model_kernels<Eval>();
     std::string msg;
     const int rc = launch_wave_set(set, *static_cast<const KernelArgs *>(kernel_args), static_cast<hipStream_t>(stream), msg);
-    if (rc && err && err_len > 0)
-    {
-        strncpy(err, msg.c_str(), (size_t)err_len - 1);
-        err[err_len - 1] = 0;
-    }
-    return rc;
+    return device_launch_result(rc, msg, err, err_len);
 }
 
-// registers in its constructor, unregisters in its destructor (the library's static object)
-struct DeviceModelRegistration
+// (the wave body's key has no parameter count)
+inline int32_t unregister_device_model(const char *name, int32_t)
 {
-    fvb_device_model descriptor;
-    bool registered;
-    DeviceModelRegistration(const char *name, fvb_device_model_launch_fn launch)
-    {
-        descriptor.name = name;
-        descriptor.abi_version = FVB_ABI_VERSION;
-        descriptor.kernel_args_size = (uint32_t)sizeof(KernelArgs);
-        descriptor.wave_layout_size = (uint32_t)sizeof(WaveLayout);
-        descriptor.launch = launch;
-        registered = fabber_vb_register_device_model(&descriptor) == 0;
-        if (!registered)
-            fprintf(stderr, "fabber: device model '%s' not registered (%s): the model runs on the host\n", name, fabber_vb_last_error());
-    }
-    ~DeviceModelRegistration()
-    {
-        if (registered)
-            (void)fabber_vb_unregister_device_model(descriptor.name);
-    }
-    DeviceModelRegistration(const DeviceModelRegistration &) = delete;
-    DeviceModelRegistration &operator=(const DeviceModelRegistration &) = delete;
-};
+    return fabber_vb_unregister_device_model(name);
+}
 } // namespace fvb
 
-#define FABBER_DEVICE_MODEL_CAT2(a, b) a##b
-#define FABBER_DEVICE_MODEL_CAT(a, b) FABBER_DEVICE_MODEL_CAT2(a, b)
-#define FABBER_DEVICE_MODEL(NAME, EVAL)                                                                      \
-    static fvb::DeviceModelRegistration FABBER_DEVICE_MODEL_CAT(fabber_device_model_registration_, __LINE__)( \
-        NAME, &fvb::device_model_launch<EVAL>);
+#define FABBER_DEVICE_MODEL(NAME, EVAL)                                                                                        \
+    static fvb::DeviceRegistration<fvb_device_model> FABBER_DEVICE_CAT(fabber_device_model_registration_, __LINE__)(           \
+        fvb_device_model{ NAME, FVB_ABI_VERSION, (uint32_t)sizeof(fvb::KernelArgs), (uint32_t)sizeof(fvb::WaveLayout),          \
+            &fvb::device_model_launch<EVAL> },                                                                                  \
+        0, &fabber_vb_register_device_model, &fvb::unregister_device_model, "", "the model runs on the host");
 
 #endif /* FABBER_DEVICE_MODEL_H */

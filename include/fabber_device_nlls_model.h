@@ -53,10 +53,6 @@
 #endif
 #include "../fabber_core_amd/csrc/vb_nlls_launch.h"
 
-#include <cstdio>
-#include <cstring>
-#include <string>
-
 namespace fvb
 {
 // lane / wave: the one kernel of the macro line, the other NULL
@@ -65,12 +61,7 @@ inline int32_t device_nlls_model_launch(NllsKernelFn lane, NllsWaveKernelFn wave
     std::string msg;
     const int rc = launch_nlls_kernel(lane, wave, lane ? NLLS_VARIANT_LANE : NLLS_VARIANT_WAVE, *static_cast<const NllsArgs *>(nlls_args),
         static_cast<hipStream_t>(stream), msg);
-    if (rc && err && err_len > 0)
-    {
-        strncpy(err, msg.c_str(), (size_t)err_len - 1);
-        err[err_len - 1] = 0;
-    }
-    return rc;
+    return device_launch_result(rc, msg, err, err_len);
 }
 
 template <class Eval>
@@ -86,49 +77,23 @@ int32_t device_nlls_lane_launch(const void *nlls_args, void *stream, char *err, 
     return device_nlls_model_launch(nlls_lane_kernel<typename LibraryLane<Eval>::template Model<P>, P>, nullptr, nlls_args, stream, err, err_len);
 }
 
-// registers in its constructor, unregisters in its destructor (the library's static object)
-struct DeviceNllsModelRegistration
+// the descriptor of one macro line (n_params 0: the wave minimiser)
+inline fvb_device_nlls_model device_nlls_model(const char *name, int32_t n_params, fvb_device_nlls_launch_fn launch)
 {
-    fvb_device_nlls_model descriptor;
-    bool registered;
-    DeviceNllsModelRegistration(const char *name, int n_params, fvb_device_nlls_launch_fn launch)
-    {
-        descriptor.name = name;
-        descriptor.abi_version = FVB_ABI_VERSION;
-        descriptor.nlls_args_size = (uint32_t)sizeof(NllsArgs);
-        descriptor.wave_layout_size = (uint32_t)sizeof(WaveLayout);
-        descriptor.n_params = n_params;
-        descriptor.launch = launch;
-        registered = fabber_vb_register_device_nlls_model(&descriptor) == 0;
-        if (!registered)
-        {
-            if (n_params == 0)
-                fprintf(stderr, "fabber: NLLS minimiser of device model '%s' not registered (%s): method=nlls evaluates the model on the host\n",
-                    name, fabber_vb_last_error());
-            else
-                fprintf(stderr, "fabber: lane NLLS minimiser of device model '%s' (%d parameters) not registered (%s): the wave minimiser is used\n",
-                    name, n_params, fabber_vb_last_error());
-        }
-    }
-    ~DeviceNllsModelRegistration()
-    {
-        if (registered)
-            (void)fabber_vb_unregister_device_nlls_model(descriptor.name, descriptor.n_params);
-    }
-    DeviceNllsModelRegistration(const DeviceNllsModelRegistration &) = delete;
-    DeviceNllsModelRegistration &operator=(const DeviceNllsModelRegistration &) = delete;
-};
+    return fvb_device_nlls_model{ name, FVB_ABI_VERSION, (uint32_t)sizeof(NllsArgs), (uint32_t)sizeof(WaveLayout), n_params, launch };
+}
 } // namespace fvb
 
-#define FABBER_DEVICE_NLLS_MODEL_CAT2(a, b) a##b
-#define FABBER_DEVICE_NLLS_MODEL_CAT(a, b) FABBER_DEVICE_NLLS_MODEL_CAT2(a, b)
-#define FABBER_DEVICE_NLLS_MODEL(NAME, EVAL)                                                                            \
-    static fvb::DeviceNllsModelRegistration FABBER_DEVICE_NLLS_MODEL_CAT(fabber_device_nlls_registration_, __LINE__)(   \
-        NAME, 0, &fvb::device_nlls_wave_launch<EVAL>);
-#define FABBER_DEVICE_NLLS_LANE_MODEL(NAME, EVAL, NPARAMS)                                                              \
-    static_assert((NPARAMS) >= 1 && (NPARAMS) <= 6,                                                                     \
-        "FABBER_DEVICE_NLLS_LANE_MODEL: the lane minimisers of a library body exist for 1 to 6 parameters");           \
-    static fvb::DeviceNllsModelRegistration FABBER_DEVICE_NLLS_MODEL_CAT(fabber_device_nlls_lane_registration_, __LINE__)( \
-        NAME, NPARAMS, &fvb::device_nlls_lane_launch<EVAL, NPARAMS>);
+#define FABBER_DEVICE_NLLS_MODEL(NAME, EVAL)                                                                                   \
+    static fvb::DeviceRegistration<fvb_device_nlls_model> FABBER_DEVICE_CAT(fabber_device_nlls_registration_, __LINE__)(       \
+        fvb::device_nlls_model(NAME, 0, &fvb::device_nlls_wave_launch<EVAL>), 0, &fabber_vb_register_device_nlls_model,         \
+        &fabber_vb_unregister_device_nlls_model, "NLLS minimiser of ", "method=nlls evaluates the model on the host");
+#define FABBER_DEVICE_NLLS_LANE_MODEL(NAME, EVAL, NPARAMS)                                                                     \
+    static_assert((NPARAMS) >= 1 && (NPARAMS) <= 6,                                                                            \
+        "FABBER_DEVICE_NLLS_LANE_MODEL: the lane minimisers of a library body exist for 1 to 6 parameters");                  \
+    static fvb::DeviceRegistration<fvb_device_nlls_model> FABBER_DEVICE_CAT(fabber_device_nlls_lane_registration_, __LINE__)(  \
+        fvb::device_nlls_model(NAME, NPARAMS, &fvb::device_nlls_lane_launch<EVAL, NPARAMS>), NPARAMS,                           \
+        &fabber_vb_register_device_nlls_model, &fabber_vb_unregister_device_nlls_model, "lane NLLS minimiser of ",             \
+        "the wave minimiser is used");
 
 #endif /* FABBER_DEVICE_NLLS_MODEL_H */

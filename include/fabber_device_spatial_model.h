@@ -77,40 +77,14 @@ int32_t device_spatial_model_launch(int32_t which, int32_t need_f, const void *s
         snprintf(err, (size_t)err_len, "spatial kernel %d of a device model: %s", (int)which, fn ? hipGetErrorString(e) : "no such kernel");
     return e == hipSuccess ? 0 : -100 - (int)e;
 }
-
-// registers in its constructor, unregisters in its destructor (the library's static object)
-struct DeviceSpatialModelRegistration
-{
-    fvb_device_spatial_model descriptor;
-    bool registered;
-    DeviceSpatialModelRegistration(const char *name, int n_params, int state_rows, fvb_device_spatial_launch_fn launch)
-    {
-        descriptor.name = name;
-        descriptor.abi_version = FVB_ABI_VERSION;
-        descriptor.spatial_args_size = (uint32_t)sizeof(SpatialArgs);
-        descriptor.n_params = n_params;
-        descriptor.state_rows = state_rows;
-        descriptor.launch = launch;
-        registered = fabber_vb_register_device_spatial_model(&descriptor) == 0;
-        if (!registered)
-            fprintf(stderr, "fabber: spatial kernels of device model '%s' (%d parameters) not registered (%s): under spatial VB the model is evaluated on the host\n",
-                name, n_params, fabber_vb_last_error());
-    }
-    ~DeviceSpatialModelRegistration()
-    {
-        if (registered)
-            (void)fabber_vb_unregister_device_spatial_model(descriptor.name, descriptor.n_params);
-    }
-    DeviceSpatialModelRegistration(const DeviceSpatialModelRegistration &) = delete;
-    DeviceSpatialModelRegistration &operator=(const DeviceSpatialModelRegistration &) = delete;
-};
 } // namespace fvb
 
-#define FABBER_DEVICE_SPATIAL_MODEL_CAT2(a, b) a##b
-#define FABBER_DEVICE_SPATIAL_MODEL_CAT(a, b) FABBER_DEVICE_SPATIAL_MODEL_CAT2(a, b)
 #define FABBER_DEVICE_SPATIAL_MODEL(NAME, EVAL, NPARAMS)                                                                     \
     static_assert((NPARAMS) >= 1 && (NPARAMS) <= 6, "FABBER_DEVICE_SPATIAL_MODEL: the spatial kernels of a library body exist for 1 to 6 parameters"); \
-    static fvb::DeviceSpatialModelRegistration FABBER_DEVICE_SPATIAL_MODEL_CAT(fabber_device_spatial_registration_, __LINE__)( \
-        NAME, NPARAMS, fvb::SpLayout<NPARAMS>::ROWS, &fvb::device_spatial_model_launch<fvb::LibraryLane<EVAL>::Model<NPARAMS>, NPARAMS>);
+    static fvb::DeviceRegistration<fvb_device_spatial_model> FABBER_DEVICE_CAT(fabber_device_spatial_registration_, __LINE__)( \
+        fvb_device_spatial_model{ NAME, FVB_ABI_VERSION, (uint32_t)sizeof(fvb::SpatialArgs), NPARAMS, fvb::SpLayout<NPARAMS>::ROWS, \
+            &fvb::device_spatial_model_launch<fvb::LibraryLane<EVAL>::Model<NPARAMS>, NPARAMS> },                              \
+        NPARAMS, &fabber_vb_register_device_spatial_model, &fabber_vb_unregister_device_spatial_model, "spatial kernels of ",  \
+        "under spatial VB the model is evaluated on the host");
 
 #endif /* FABBER_DEVICE_SPATIAL_MODEL_H */

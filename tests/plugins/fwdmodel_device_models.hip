@@ -13,16 +13,16 @@
 // 2 (invrec's body) let the two halves be compiled side by side; undefined = everything.
 #if !defined(FABBER_TEST_PART) || FABBER_TEST_PART == 1
 #define FABBER_TEST_HOST 1
-#define FABBER_TEST_MULTIEXP 1
+#define FABBER_TEST_MULTIEXP_WAVE 1
 #endif
 #if !defined(FABBER_TEST_PART) || FABBER_TEST_PART == 2
-#define FABBER_TEST_INVREC 1
+#define FABBER_TEST_INVREC_WAVE 1
 #endif
 
 #include "fabber_device_model.h"
 
 // ---- device bodies ----------------------------------------------------------------------------------------------
-#ifdef FABBER_TEST_MULTIEXP
+#ifdef FABBER_TEST_MULTIEXP_WAVE
 namespace // (a body's kernels and launcher are template instantiations on it: keep its name to this library)
 {
 struct MultiExpBody
@@ -42,7 +42,7 @@ struct MultiExpBody
 FABBER_DEVICE_MODEL("multiexp_dev", MultiExpBody)
 #endif
 
-#ifdef FABBER_TEST_INVREC
+#ifdef FABBER_TEST_INVREC_WAVE
 namespace
 {
 struct InvRecBody
@@ -62,161 +62,8 @@ struct InvRecBody
 FABBER_DEVICE_MODEL("invrec", InvRecBody)
 #endif
 
-// ---- host side --------------------------------------------------------------------------------------------------
-#ifdef FABBER_TEST_HOST
-#include "fabber_core/fwdmodel.h"
-#include "fabber_core/priors.h"
-#include "fabber_core/transforms.h"
-
-#include <cmath>
-#include <string>
-#include <vector>
-
-class MultiExpDevFwdModel : public FwdModel
-{
-public:
-    static FwdModel *NewInstance()
-    {
-        return new MultiExpDevFwdModel();
-    }
-    void GetOptions(std::vector<OptionSpec> &opts) const
-    {
-        OptionSpec dt = { "dt", OPT_FLOAT, "Time between samples", OPT_REQ, "" };
-        OptionSpec num = { "num-exps", OPT_INT, "Number of exponentials", OPT_NONREQ, "1" };
-        opts.push_back(dt);
-        opts.push_back(num);
-    }
-    std::string GetDescription() const
-    {
-        return "sum of decaying exponentials: amp1 exp(-r1 t) + amp2 exp(-r2 t) + ... (with a device body)";
-    }
-    std::string ModelVersion() const
-    {
-        return "test";
-    }
-    void Initialize(FabberRunData &args)
-    {
-        FwdModel::Initialize(args);
-        m_dt = args.GetDouble("dt", 0);
-        m_num = args.GetIntDefault("num-exps", 1, 1);
-    }
-    void EvaluateModel(const NEWMAT::ColumnVector &params, NEWMAT::ColumnVector &result, const std::string & = "") const
-    {
-        result.ReSize(data.Nrows());
-        for (int t = 1; t <= result.Nrows(); t++)
-        {
-            const double tt = double(t - 1) * m_dt;
-            double sum = 0;
-            for (int i = 0; i < m_num; i++)
-                sum += params(2 * i + 1) * std::exp(-params(2 * i + 2) * tt);
-            result(t) = sum;
-        }
-    }
-    // data-dependent initial posterior: the first amplitude starts at the first sample
-    void InitVoxelPosterior(MVNDist &posterior) const
-    {
-        posterior.means(1) = data(1);
-    }
-    bool GetDeviceModel(DeviceModelSpec &spec) const
-    {
-        spec.device_model = "multiexp_dev";
-        spec.iopt[0] = m_num;
-        spec.dopt[0] = m_dt;
-        return true;
-    }
-
-protected:
-    void GetParameterDefaults(std::vector<Parameter> &params) const
-    {
-        params.clear();
-        for (int i = 0; i < m_num; i++)
-        {
-            params.push_back(Parameter(2 * i, "amp" + stringify(i + 1), DistParams(1, 1e6), DistParams(1, 1e6)));
-            params.push_back(Parameter(2 * i + 1, "r" + stringify(i + 1), DistParams(1, 100), DistParams(1, 1.5), PRIOR_NORMAL,
-                TRANSFORM_LOG())); // (a LOG-transformed variance of exactly 1 is log(1) = 0 in Fabber space: a singular posterior)
-        }
-    }
-    double m_dt;
-    int m_num;
-};
-
-class InvRecFwdModel : public FwdModel
-{
-public:
-    static FwdModel *NewInstance()
-    {
-        return new InvRecFwdModel();
-    }
-    void GetOptions(std::vector<OptionSpec> &opts) const
-    {
-        OptionSpec ti = { "ti<n>", OPT_FLOAT, "Inversion times, one per timepoint: ti1, ti2, ...", OPT_REQ, "" };
-        opts.push_back(ti);
-    }
-    std::string GetDescription() const
-    {
-        return "inversion recovery: M0 (1 - 2 a exp(-TI / T1)) (with a device body)";
-    }
-    std::string ModelVersion() const
-    {
-        return "test";
-    }
-    void Initialize(FabberRunData &args)
-    {
-        FwdModel::Initialize(args);
-        m_tis = args.GetDoubleList("ti", 0);
-        if (m_tis.empty())
-            throw InvalidOptionValue("ti1", "", "The inversion times ti1, ti2, ... are required");
-    }
-    void EvaluateModel(const NEWMAT::ColumnVector &params, NEWMAT::ColumnVector &result, const std::string & = "") const
-    {
-        if (data.Nrows() != (int)m_tis.size())
-            throw InvalidOptionValue("ti<n>", stringify(m_tis.size()) + " values", "One inversion time per timepoint is needed");
-        result.ReSize(data.Nrows());
-        for (int t = 1; t <= result.Nrows(); t++)
-            result(t) = params(1) * (1.0 - 2.0 * params(3) * std::exp(-m_tis[t - 1] / params(2)));
-    }
-    // M0 starts at the largest magnitude of the series
-    void InitVoxelPosterior(MVNDist &posterior) const
-    {
-        double m = 0;
-        for (int t = 1; t <= data.Nrows(); t++)
-            m = std::fabs(data(t)) > m ? std::fabs(data(t)) : m;
-        if (m > 0)
-            posterior.means(1) = m;
-    }
-    bool GetDeviceModel(DeviceModelSpec &spec) const
-    {
-        spec.device_model = "invrec";
-        spec.constants = m_tis;
-        return true;
-    }
-
-protected:
-    void GetParameterDefaults(std::vector<Parameter> &params) const
-    {
-        params.clear();
-        params.push_back(Parameter(0, "M0", DistParams(1, 1e6), DistParams(1, 1e6)));
-        params.push_back(Parameter(1, "T1", DistParams(1, 100), DistParams(1, 1.5), PRIOR_NORMAL, TRANSFORM_LOG()));
-        params.push_back(Parameter(2, "a", DistParams(0.8, 4), DistParams(0.8, 1), PRIOR_NORMAL, TRANSFORM_FRACTIONAL()));
-    }
-    std::vector<double> m_tis;
-};
-
-// the three hooks fabber_load_models reads (fwdmodel.cc:25-27)
-extern "C" {
-int get_num_models()
-{
-    return 2;
-}
-const char *get_model_name(int index)
-{
-    return index == 0 ? "multiexp_dev" : (index == 1 ? "invrec" : 0);
-}
-NewInstanceFptr get_new_instance_func(const char *name)
-{
-    if (std::string(name) == "multiexp_dev")
-        return MultiExpDevFwdModel::NewInstance;
-    return std::string(name) == "invrec" ? InvRecFwdModel::NewInstance : 0;
-}
-}
-#endif
+#define FABBER_TEST_OWN_BODIES 1 // (above: not inlined by force, each compiled in its part only)
+#define FABBER_TEST_MULTIEXP "multiexp_dev"
+#define FABBER_TEST_INVREC "invrec"
+#define FABBER_TEST_WITH "a device body"
+#include "test_device_models.h"

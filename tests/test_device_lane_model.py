@@ -12,18 +12,18 @@ import numpy as np
 import pytest
 
 import cases
-import lane_model_lib
+import device_model_lib
 import oracle
 import parity
 from fabber_core_amd import fabber, hiplib, vbabi
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not lane_model_lib.engine_built(), reason="engine not built")]
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not device_model_lib.engine_built(), reason="engine not built")]
 
 
 @pytest.fixture(scope="module")
 def library():
     assert hiplib.available() and hiplib.device_count() > 0
-    path = lane_model_lib.build_library()
+    path = device_model_lib.build_lane_library()
     hiplib.load_model_library(path)
     assert {("multiexp_lane", 2), ("multiexp_lane", 4), ("invrec_lane", 3)} <= set(hiplib.device_lane_models())
     return path

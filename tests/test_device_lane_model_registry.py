@@ -10,16 +10,15 @@ import numpy as np
 import pytest
 
 import device_model_lib
-import lane_model_lib
 from fabber_core_amd import hiplib, vbabi
 
-pytestmark = [pytest.mark.skipif(not lane_model_lib.engine_built(), reason="engine not built")]
+pytestmark = [pytest.mark.skipif(not device_model_lib.engine_built(), reason="engine not built")]
 
 
 @pytest.fixture(scope="module")
 def library():
-    path = lane_model_lib.build_library()
-    print("lane model library: compile seconds per part %s" % {k: round(v, 1) for k, v in sorted(lane_model_lib.seconds.items())})
+    path = device_model_lib.build_lane_library()
+    print("lane model library: compile seconds per part %s" % {k: round(v, 1) for k, v in sorted(device_model_lib.seconds["libfabber_models_lane.so"].items())})
     hiplib.load_model_library(path)
     return path
 

@@ -105,3 +105,55 @@ def test_config_carries_name_and_constants(library):
     assert h.cfg.model == vbabi.MODEL_PLUGIN and h.cfg.device_model == b"invrec"
     assert h.cfg.n_model_consts == 12 and h.cfg.model_consts == h.keep["constants"].ctypes.data
     assert h.cfg.n_params == 3 and h.cfg.transform[2] == vbabi.TRANSFORM_FRACTIONAL
+
+
+def _refused_sizes(descriptor, register, code):
+    """the struct sizes of the engine, in the order its refusal of a descriptor that states 0 for each names them"""
+    assert register(C.byref(descriptor)) == code
+    return [int(n) for n in re.findall(r"\w+ 0 against (\d+)", hiplib.lib().fabber_vb_last_error().decode())]
+
+
+def test_the_four_registries_keep_their_entries_apart():
+    """One name in all four registries (the NLLS one holds its wave entry next to the lane entry); taking it out of the
+    lane registry leaves the other three as they were. Never-launched descriptors: no library, no GPU."""
+    L, abi, name = hiplib.lib(), vbabi.FVB_ABI_VERSION, "apart_model"
+    launch = {cls: cls.LAUNCH_FN(lambda *args: -1) for cls in (vbabi.FvbDeviceModel, vbabi.FvbDeviceLaneModel, vbabi.FvbDeviceNllsModel,
+                                                                 vbabi.FvbDeviceSpatialModel)}
+    wave_sizes = _refused_sizes(vbabi.FvbDeviceModel(b"size_probe", abi, 0, 0, launch[vbabi.FvbDeviceModel]), L.fabber_vb_register_device_model, -72)
+    lane_sizes = _refused_sizes(vbabi.FvbDeviceLaneModel(b"size_probe", abi, 0, 3, 0, launch[vbabi.FvbDeviceLaneModel]),
+                                L.fabber_vb_register_device_lane_model, -72)
+    nlls_sizes = _refused_sizes(vbabi.FvbDeviceNllsModel(b"size_probe", abi, 0, 0, 3, launch[vbabi.FvbDeviceNllsModel]),
+                                L.fabber_vb_register_device_nlls_model, -72)
+    spatial_sizes = _refused_sizes(vbabi.FvbDeviceSpatialModel(b"size_probe", abi, 0, 3, 0, launch[vbabi.FvbDeviceSpatialModel]),
+                                   L.fabber_vb_register_device_spatial_model, -77)
+    assert (len(wave_sizes), len(lane_sizes), len(nlls_sizes), len(spatial_sizes)) == (2, 1, 2, 1)
+    wave = vbabi.FvbDeviceModel(name.encode(), abi, wave_sizes[0], wave_sizes[1], launch[vbabi.FvbDeviceModel])
+    lane = vbabi.FvbDeviceLaneModel(name.encode(), abi, lane_sizes[0], 3, 30, launch[vbabi.FvbDeviceLaneModel])
+    nlls_wave = vbabi.FvbDeviceNllsModel(name.encode(), abi, nlls_sizes[0], nlls_sizes[1], 0, launch[vbabi.FvbDeviceNllsModel])
+    nlls_lane = vbabi.FvbDeviceNllsModel(name.encode(), abi, nlls_sizes[0], nlls_sizes[1], 3, launch[vbabi.FvbDeviceNllsModel])
+    spatial = vbabi.FvbDeviceSpatialModel(name.encode(), abi, spatial_sizes[0], 3, 0, launch[vbabi.FvbDeviceSpatialModel])
+    undo = []
+    try:
+        hiplib.register_device_model(wave)
+        undo.append(lambda: hiplib.unregister_device_model(name))
+        hiplib.register_device_lane_model(lane)
+        undo.append(lambda: hiplib.unregister_device_lane_model(name, 3))
+        for d in (nlls_wave, nlls_lane):
+            hiplib.register_device_nlls_model(d)
+            undo.append(lambda n=d.n_params: hiplib.unregister_device_nlls_model(name, n))
+        hiplib.register_device_spatial_model(spatial)
+        undo.append(lambda: hiplib.unregister_device_spatial_model(name, 3))
+        assert name in hiplib.device_models() and (name, 3) in hiplib.device_lane_models()
+        assert {(name, 0), (name, 3)} <= set(hiplib.device_nlls_models()) and (name, 3) in hiplib.device_spatial_models()
+        counts = (len(hiplib.device_models()), len(hiplib.device_nlls_models()), len(hiplib.device_spatial_models()))
+
+        undo.pop(1)()  # the lane entry, and nothing else
+        assert name not in [n for n, _ in hiplib.device_lane_models()]
+        assert name in hiplib.device_models()
+        assert {(name, 0), (name, 3)} <= set(hiplib.device_nlls_models())
+        assert (name, 3) in hiplib.device_spatial_models()
+        assert counts == (len(hiplib.device_models()), len(hiplib.device_nlls_models()), len(hiplib.device_spatial_models()))
+    finally:
+        for step in reversed(undo):
+            step()
+    assert name not in hiplib.device_models() and name not in [n for n, _ in hiplib.device_nlls_models() + hiplib.device_spatial_models()]

@@ -15,11 +15,10 @@ import scipy.optimize
 
 import cases
 import device_model_lib
-import nlls_model_lib
 import oracle
 from fabber_core_amd import fabber, hiplib, vbabi
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not nlls_model_lib.engine_built(), reason="engine not built")]
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not device_model_lib.engine_built(), reason="engine not built")]
 
 ENTRIES = {("multiexp_nlls", 0), ("multiexp_nlls", 2), ("multiexp_nlls", 4), ("invrec_nlls", 0), ("invrec_nlls", 3)}
 
@@ -27,7 +26,7 @@ ENTRIES = {("multiexp_nlls", 0), ("multiexp_nlls", 2), ("multiexp_nlls", 4), ("i
 @pytest.fixture(scope="module")
 def library():
     assert hiplib.available() and hiplib.device_count() > 0
-    path = nlls_model_lib.build_library()
+    path = device_model_lib.build_nlls_library()
     hiplib.load_model_library(path)
     assert ENTRIES <= set(hiplib.device_nlls_models())
     return path

@@ -10,16 +10,15 @@ import numpy as np
 import pytest
 
 import device_model_lib
-import nlls_model_lib
 from fabber_core_amd import hiplib, vbabi
 
-pytestmark = [pytest.mark.skipif(not nlls_model_lib.engine_built(), reason="engine not built")]
+pytestmark = [pytest.mark.skipif(not device_model_lib.engine_built(), reason="engine not built")]
 
 
 @pytest.fixture(scope="module")
 def library():
-    path = nlls_model_lib.build_library()
-    print("NLLS model library: compile seconds per part %s" % {k: round(v, 1) for k, v in sorted(nlls_model_lib.seconds.items())})
+    path = device_model_lib.build_nlls_library()
+    print("NLLS model library: compile seconds per part %s" % {k: round(v, 1) for k, v in sorted(device_model_lib.seconds["libfabber_models_nlls.so"].items())})
     hiplib.load_model_library(path)
     return path
 

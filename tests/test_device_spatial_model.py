@@ -12,11 +12,11 @@ import pytest
 
 import oracle
 import parity
-import spatial_model_lib
+import device_model_lib
 from fabber_core_amd import fabber, hiplib, vbabi
 from test_spatial import masked_volume, smooth_exp_data
 
-pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not spatial_model_lib.engine_built(), reason="engine not built")]
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not device_model_lib.engine_built(), reason="engine not built")]
 
 SHAPE, T, DT = (7, 6, 5), 21, 0.04
 
@@ -24,7 +24,7 @@ SHAPE, T, DT = (7, 6, 5), 21, 0.04
 @pytest.fixture(scope="module")
 def library():
     assert hiplib.available() and hiplib.device_count() > 0
-    path = spatial_model_lib.build_library()
+    path = device_model_lib.build_spatial_library()
     hiplib.load_model_library(path)
     assert {("multiexp_sp", 2), ("multiexp_sp", 4), ("invrec_sp", 3)} <= set(hiplib.device_spatial_models())
     return path

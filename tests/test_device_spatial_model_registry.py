@@ -11,16 +11,15 @@ import numpy as np
 import pytest
 
 import device_model_lib
-import spatial_model_lib
 from fabber_core_amd import hiplib, vbabi
 
-pytestmark = [pytest.mark.skipif(not spatial_model_lib.engine_built(), reason="engine not built")]
+pytestmark = [pytest.mark.skipif(not device_model_lib.engine_built(), reason="engine not built")]
 
 
 @pytest.fixture(scope="module")
 def library():
-    path = spatial_model_lib.build_library()
-    print("spatial model library: compile seconds per part %s" % {k: round(v, 1) for k, v in sorted(spatial_model_lib.seconds.items())})
+    path = device_model_lib.build_spatial_library()
+    print("spatial model library: compile seconds per part %s" % {k: round(v, 1) for k, v in sorted(device_model_lib.seconds["libfabber_models_spatial.so"].items())})
     hiplib.load_model_library(path)
     return path
 

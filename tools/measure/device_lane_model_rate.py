@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 import cases
-import lane_model_lib
+import device_model_lib
 from fabber_core_amd import fabber, hiplib, vbabi
 from fabber_core_amd.device import DeviceProblem
 
@@ -33,7 +33,7 @@ ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--json", default=None)
 args = ap.parse_args()
 
-library = lane_model_lib.build_library()
+library = device_model_lib.build_lane_library()
 hiplib.load_model_library(library)
 T, DT, ITS = 50, 0.04, 10
 ROUTES = (("lane<multiexp_lane,2>", "plugin", "auto"), ("wave<multiexp_lane>", "plugin", "wave"), ("lane<exp,2>", "exp", "auto"))

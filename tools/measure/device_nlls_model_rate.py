@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 import cases
-import nlls_model_lib
+import device_model_lib
 from fabber_core_amd import fabber, hiplib, vbabi
 
 ap = argparse.ArgumentParser()
@@ -36,7 +36,7 @@ ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--json", default=None)
 args = ap.parse_args()
 
-library = nlls_model_lib.build_library()
+library = device_model_lib.build_nlls_library()
 hiplib.load_model_library(library)
 T, DT = 50, 0.04
 ROUTES = (("nlls<multiexp_nlls,2>", "plugin", "auto"), ("nlls_wave<multiexp_nlls>", "plugin", "wave"), ("nlls<exp,2>", "exp", "auto"))

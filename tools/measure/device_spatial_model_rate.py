@@ -26,7 +26,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 
-import spatial_model_lib
+import device_model_lib
 from fabber_core_amd import fabber, hiplib, vbabi
 from fabber_core_amd.device import DeviceProblem
 
@@ -35,7 +35,7 @@ ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--json", default=None)
 args = ap.parse_args()
 
-library = spatial_model_lib.build_library()
+library = device_model_lib.build_spatial_library()
 hiplib.load_model_library(library)
 SHAPE, T, DT, ITERS, SHORT = (64, 64, 24), 50, 0.04, 10, 2
 rng = np.random.default_rng(0)
