@@ -163,7 +163,7 @@ void NLLSInferenceTechnique::DoCalculations(FabberRunData &rundata)
         spec = DeviceModelSpec();
         spec.model = FVB_MODEL_HOSTJAC;
     }
-    // (model fit and residuals of a library's model come from its host code, as under VB)
+    // (model fit and residuals of a library's model: SaveEngineResults asks for its result-image kernel, as under VB)
     st.host_model = !device_model || st.library_device_model;
     cfg.model = spec.model;
     for (int i = 0; i < 4; i++)

@@ -979,17 +979,52 @@ void InferenceTechnique::SaveEngineResults(FabberRunData &rundata, const fvb_con
 
     if (V > 0)
     {
-        if (host_model) // the model prediction can only come from the model's own host code
-            pp.modelfit = pp.residuals = NULL;
         fvb_config pcfg = cfg;
+        // host_model says which route the FIT took. The prediction depends on the posterior means only: a model of a
+        // library takes it from its device body wherever the library compiled the result-image kernel around it
+        // (include/fabber_device_results_model.h) - also after a fit on the host route (a library without spatial
+        // kernels or minimisers) - unless host-model asks for the host code.
+        std::vector<double> constants;
+        bool device_fit = false;
+        if (host_model && (want_fit || want_resid) && !rundata.GetBool("host-model"))
+        {
+            DeviceModelSpec spec;
+            if (m_model->GetDeviceModel(spec) && !spec.device_model.empty() && spec.device_model.size() < sizeof(pcfg.device_model))
+            {
+                fvb_config named = cfg;
+                named.model = FVB_MODEL_PLUGIN;
+                named.design = NULL;
+                for (int i = 0; i < 4; i++)
+                {
+                    named.model_iopt[i] = spec.iopt[i];
+                    named.model_dopt[i] = spec.dopt[i];
+                }
+                memset(named.device_model, 0, sizeof(named.device_model));
+                strncpy(named.device_model, spec.device_model.c_str(), sizeof(named.device_model) - 1);
+                constants = spec.constants;
+                named.model_consts = constants.empty() ? NULL : constants.data();
+                named.n_model_consts = (int32_t)constants.size();
+                const string kernel = fabber_vb_postproc_kernel_name(&named);
+                if (kernel.compare(0, 9, "postproc<") == 0)
+                {
+                    LOG << "InferenceTechnique::model fit and residuals with the body '" << named.device_model
+                        << "' of its library (kernel " << kernel << ")" << endl;
+                    pcfg = named;
+                    device_fit = true;
+                }
+            }
+        }
+        const bool host_fit = host_model && !device_fit; // the model prediction can only come from the model's own host code
+        if (host_fit)
+            pp.modelfit = pp.residuals = NULL;
         int series_rows = 0, series_cols = 0;
         // (only the residuals need the series on the device: not uploaded otherwise)
-        const void *series = (pp.residuals != NULL) ? engine_series(rundata, host_model, pcfg.data_f64, series_rows, series_cols) : NULL;
+        const void *series = (pp.residuals != NULL) ? engine_series(rundata, host_fit, pcfg.data_f64, series_rows, series_cols) : NULL;
         int rc = fabber_vb_postproc_host(&pcfg, series, m_result_image.Store(), &pp, rundata.GetIntDefault("device", 0, 0));
         if (rc != 0)
             throw FabberInternalError(string("MI355X engine failed in post-processing: ") + fabber_vb_last_error());
         timer.lap("post-processing kernel (host pointers)");
-        if (host_model && (want_fit || want_resid)) // inference.cc:181-243
+        if (host_fit && (want_fit || want_resid)) // inference.cc:181-243
         {
             const Matrix &data = rundata.GetMainVoxelData();
             const Matrix &coords = rundata.GetVoxelCoords();
@@ -1015,6 +1050,7 @@ void InferenceTechnique::SaveEngineResults(FabberRunData &rundata, const fvb_con
                         resid[(size_t)t * V + v] = data.at0(t, v) - tmp(t + 1);
                 }
             }
+            timer.lap("model fit and residuals on the host (one thread)");
         }
     }
     for (int k = 0; k < P; k++)
@@ -1081,7 +1117,7 @@ void Vb::SaveResults(FabberRunData &rundata) const
 {
     LOG << "Vb::Preparing to save results..." << endl;
     SaveEngineResults(rundata, m_store->cfg, m_store->params, m_noise_params, m_noise->NumParams(),
-        !m_store->has_device_model || m_store->library_device_model); // (model fit and residuals of a library's model: its host code)
+        !m_store->has_device_model || m_store->library_device_model); // (a library's model: SaveEngineResults asks for its result-image kernel)
     const int V = m_nvoxels;
     if (m_saveF && m_needF && !m_free_energy.empty())
     {

@@ -9,6 +9,7 @@
 #include "vb_host_stage.h"
 #include "vb_device_registry.h"
 #include "vb_wave_kernel.h"
+#include "vb_postproc_kernel.h"
 
 #include <hip/hip_runtime.h>
 
@@ -71,6 +72,29 @@ template <> struct DeviceRegistryTraits<fvb_device_lane_model>
     static std::string absent(const std::string &name, int n_params)
     {
         return "no lane kernels of a device model '" + name + "' with " + std::to_string(n_params) + " parameters are registered";
+    }
+};
+// ... and the result-image kernel of such bodies (include/fabber_device_results_model.h), by name: the kernel takes any
+// parameter count. Looked into only for a name the first registry holds.
+template <> struct DeviceRegistryTraits<fvb_device_results_model>
+{
+    static constexpr const char *noun = "device results model", *is = "is";
+    static constexpr int first_code = -80;
+    static std::vector<DeviceStructSize> sizes(const fvb_device_results_model &m)
+    {
+        return { { "fvb_config", m.config_size, sizeof(fvb_config) }, { "fvb_postproc", m.postproc_size, sizeof(fvb_postproc) } };
+    }
+    static const char *bad_params(const fvb_device_results_model &)
+    {
+        return nullptr;
+    }
+    static std::string entry(const std::string &name, int)
+    {
+        return "the result-image kernel of a device model named '" + name + "'";
+    }
+    static std::string absent(const std::string &name, int)
+    {
+        return "no result-image kernel of a device model '" + name + "' is registered";
     }
 };
 } // namespace fvb
@@ -278,70 +302,42 @@ LaneRoute select_lane(const fvb_config *cfg)
     return route;
 }
 
+// Where the model fit and the residuals of a (validated) configuration come from: the engine's kernel for its own
+// models; for a body of a model library the kernel its library compiled around it (include/fabber_device_results_model.h)
+// - an entry counts next to a wave body of its name - and without one nothing: the engine has no evaluator for the body.
+struct PostprocRoute
+{
+    bool fit = false;                               // a model fit can be computed
+    fvb_device_results_launch_fn library = nullptr; // ... by this launcher (NULL: by the engine's kernel)
+    std::string name;                               // fabber_vb_postproc_kernel_name
+};
+
+PostprocRoute select_postproc(const fvb_config *cfg)
+{
+    PostprocRoute route;
+    if (cfg->model != FVB_MODEL_PLUGIN)
+    {
+        route.fit = true;
+        route.name = "postproc";
+        return route;
+    }
+    const std::string model = config_device_model(cfg);
+    fvb_device_results_model entry;
+    if (find_wave_body(model) && DeviceRegistry<fvb_device_results_model>::instance().find(model, 0, &entry))
+    {
+        route.fit = true;
+        route.library = entry.launch;
+        route.name = "postproc<" + model + ">";
+    }
+    return route;
+}
+
+thread_local std::string g_postproc_kernel_name;
+
 bool needs_save(const fvb_config *cfg)
 {
     return cfg->convergence == FVB_CONV_FREDUCE || cfg->convergence == FVB_CONV_TRIALMODE
         || cfg->convergence == FVB_CONV_LM;
-}
-
-// ---- post-processing kernel: InferenceTechnique::SaveResults / Vb::SaveResults ----------------
-template <int MAXP>
-__global__ __launch_bounds__(256) void vb_postproc_kernel(
-    const fvb_config cfg, const void *data, const double *mvn, const fvb_postproc pp, const int n_noise)
-{
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= cfg.n_voxels)
-        return;
-    const size_t V = (size_t)cfg.n_voxels;
-    const int P = cfg.n_params, n = P + n_noise, T = cfg.n_times;
-    const int nCov = n * (n + 1) / 2;
-    double means[MAXP];
-    for (int p = 0; p < P; p++)
-    {
-        const double m = mvn[(size_t)(nCov + p) * V + v];
-        const double var = mvn[(size_t)(p * (p + 1) / 2 + p) * V + v];
-        const int tr = cfg.params_ext ? cfg.params_ext->transform[p] : cfg.transform[p];
-        // FwdModel::ToModel, fwdmodel.cc:326-337
-        const double mm = to_model(tr, m);
-        const double mv = to_model_var(tr, var);
-        const double sd = sqrt(mv);
-        means[p] = mm; // model-space value, what EvaluateModel receives
-        if (pp.mean)
-            pp.mean[(size_t)p * V + v] = mm;
-        if (pp.var)
-            pp.var[(size_t)p * V + v] = mv;
-        if (pp.std)
-            pp.std[(size_t)p * V + v] = sd;
-        if (pp.zstat)
-            pp.zstat[(size_t)p * V + v] = mm / sd;
-    }
-    for (int i = 0; i < n_noise; i++) // inference_vb.cc:981-989
-    {
-        const int q = P + i;
-        if (pp.noise_mean)
-            pp.noise_mean[(size_t)i * V + v] = mvn[(size_t)(nCov + q) * V + v];
-        if (pp.noise_std)
-            pp.noise_std[(size_t)i * V + v] = sqrt(mvn[(size_t)(q * (q + 1) / 2 + q) * V + v]);
-    }
-    if (pp.modelfit || pp.residuals) // inference.cc:181-243
-    {
-        ModelArgs ma;
-        ma.iopt0 = cfg.model_iopt[0];
-        ma.dopt0 = cfg.model_dopt[0];
-        ma.design = cfg.design;
-        for (int t = 0; t < T; t++)
-        {
-            const double fit = eval_model_runtime(cfg.model, ma, P, t, means);
-            if (pp.modelfit)
-                pp.modelfit[(size_t)t * V + v] = fit;
-            if (pp.residuals)
-            {
-                const size_t idx = (size_t)t * V + v;
-                const double y = cfg.data_f64 ? ((const double *)data)[idx] : (double)((const float *)data)[idx];
-                pp.residuals[idx] = y - fit;
-            }
-        }
-    }
 }
 
 } // namespace
@@ -1296,6 +1292,34 @@ int32_t fabber_vb_run_host_multi(const fvb_config *cfg, const void *data, const 
     return 0;
 }
 
+int32_t fabber_vb_register_device_results_model(const fvb_device_results_model *model)
+{
+    return DeviceRegistry<fvb_device_results_model>::instance().add(model);
+}
+
+int32_t fabber_vb_unregister_device_results_model(const char *name)
+{
+    return DeviceRegistry<fvb_device_results_model>::instance().remove(name, 0);
+}
+
+int32_t fabber_vb_device_results_model_count(void)
+{
+    return DeviceRegistry<fvb_device_results_model>::instance().count();
+}
+
+const char *fabber_vb_device_results_model_name(int32_t i)
+{
+    return DeviceRegistry<fvb_device_results_model>::instance().name(i);
+}
+
+const char *fabber_vb_postproc_kernel_name(const fvb_config *cfg)
+{
+    if (validate(cfg, true, true) != 0)
+        return "";
+    g_postproc_kernel_name = select_postproc(cfg).name;
+    return g_postproc_kernel_name.c_str();
+}
+
 int32_t fabber_vb_postproc_device(const fvb_config *cfg, const void *data, const double *mvn, const fvb_postproc *pp,
     void *stream)
 {
@@ -1306,16 +1330,22 @@ int32_t fabber_vb_postproc_device(const fvb_config *cfg, const void *data, const
         return fail(-22, "mvn / postproc outputs are NULL");
     if ((pp->residuals) && !data)
         return fail(-21, "residuals need the data");
+    const bool want_fit = pp->modelfit || pp->residuals;
+    const PostprocRoute route = select_postproc(cfg);
+    if (want_fit && !route.fit)
+        return fail(-85, "model fit / residuals of the device model '" + config_device_model(cfg)
+                + "': its library registered no result-image kernel for it (FABBER_DEVICE_RESULTS_MODEL in "
+                  "include/fabber_device_results_model.h); the engine cannot evaluate the body itself");
     if (cfg->n_voxels == 0)
         return 0;
-    const unsigned grid = (unsigned)((cfg->n_voxels + 255) / 256);
-    if (cfg->n_params > FVB_MAX_PARAMS)
-        hipLaunchKernelGGL(vb_postproc_kernel<FVB_MAX_PARAMS_EXT>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *cfg, data, mvn, *pp,
-            noise_outputs(cfg));
-    else
-        hipLaunchKernelGGL(vb_postproc_kernel<FVB_MAX_PARAMS>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *cfg, data, mvn, *pp,
-            noise_outputs(cfg));
-    FVB_HIP_CHECK(hipGetLastError());
+    if (want_fit && route.library)
+    {
+        char err[256] = "";
+        rc = route.library(cfg, data, mvn, pp, noise_outputs(cfg), stream, err, (int32_t)sizeof(err));
+        return rc ? fail(rc, "result-image kernel of the device model '" + config_device_model(cfg) + "': " + err) : 0;
+    }
+    // (means, variances and noise images need no model: the engine's kernel, whatever the model)
+    FVB_HIP_CHECK(launch_postproc<BuiltinEval>(*cfg, data, mvn, *pp, noise_outputs(cfg), (hipStream_t)stream));
     return 0;
 }
 
@@ -1335,7 +1365,7 @@ int32_t fabber_vb_postproc_host(const fvb_config *cfg, const void *data, const d
     const int rows = fabber_vb_mvn_rows(P + N);
     const size_t esz = cfg->data_f64 ? 8 : 4;
     fvb_config d = *cfg;
-    DevMem b_data, b_design, b_mvn;
+    DevMem b_data, b_design, b_consts, b_mvn;
     DeviceParamTable ptable;
     if (cfg->params_ext)
     {
@@ -1356,6 +1386,13 @@ int32_t fabber_vb_postproc_host(const fvb_config *cfg, const void *data, const d
         if ((rc = upload_array(b_design, cfg->design, sizeof(double) * T * P, nullptr)) != 0)
             return rc;
         d.design = (const double *)b_design.p;
+    }
+    d.model_consts = nullptr; // (a host pointer: the kernel of a library's body reads the device copy, no other kernel reads any)
+    if (cfg->model == FVB_MODEL_PLUGIN && cfg->model_consts && cfg->n_model_consts > 0)
+    {
+        if ((rc = upload_array(b_consts, cfg->model_consts, sizeof(double) * (size_t)cfg->n_model_consts, nullptr)) != 0)
+            return rc;
+        d.model_consts = (const double *)b_consts.p;
     }
     FVB_HIP_CHECK(b_mvn.alloc(sizeof(double) * rows * V));
     {

@@ -34,8 +34,13 @@ struct DeviceStructSize
 //   absent(name, n_params)      what unregistering an entry that is not there is told
 template <class D> struct DeviceRegistryTraits;
 
-// The key of an entry is (name, parameter count); the wave body's descriptor has no count: 0
+// The key of an entry is (name, parameter count); the descriptors of the wave body and of the result-image kernel have
+// no count: 0
 inline int registered_params(const fvb_device_model &)
+{
+    return 0;
+}
+inline int registered_params(const fvb_device_results_model &)
 {
     return 0;
 }

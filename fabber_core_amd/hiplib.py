@@ -21,7 +21,8 @@ _LIB = None
 _DEVICE_ENTRIES = (("device_model", vbabi.FvbDeviceModel, False),
                    ("device_lane_model", vbabi.FvbDeviceLaneModel, True),
                    ("device_nlls_model", vbabi.FvbDeviceNllsModel, True),
-                   ("device_spatial_model", vbabi.FvbDeviceSpatialModel, True))
+                   ("device_spatial_model", vbabi.FvbDeviceSpatialModel, True),
+                   ("device_results_model", vbabi.FvbDeviceResultsModel, False))
 
 
 class HipEngineError(RuntimeError):
@@ -97,6 +98,8 @@ def lib():
         L.fabber_nlls_kernel_name.argtypes = [cfgp]
         L.fabber_vb_spatial_kernel_name.restype = C.c_char_p
         L.fabber_vb_spatial_kernel_name.argtypes = [cfgp]
+        L.fabber_vb_postproc_kernel_name.restype = C.c_char_p
+        L.fabber_vb_postproc_kernel_name.argtypes = [cfgp]
         if L.fabber_vb_abi_version() != vbabi.FVB_ABI_VERSION:
             raise HipEngineError("libfabber_vb_hip.so ABI version mismatch: rebuild")
         _LIB = L
@@ -149,7 +152,7 @@ def device_models():
 
 def register_device_model(descriptor):
     """fabber_vb_register_device_model with a vbabi.FvbDeviceModel (the caller keeps it alive); raises with the engine's
-    message when the registration is refused. The three below: the same with the descriptor class of their kind."""
+    message when the registration is refused. The four below: the same with the descriptor class of their kind."""
     _register("device_model", descriptor)
 
 
@@ -197,8 +200,28 @@ def unregister_device_spatial_model(name, n_params):
     _unregister("device_spatial_model", name, n_params)
 
 
+def device_results_models():
+    """Names of the result-image kernels registered with the engine (include/fabber_device_results_model.h)."""
+    return _listed("device_results_model", False)
+
+
+def register_device_results_model(descriptor):
+    _register("device_results_model", descriptor)
+
+
+def unregister_device_results_model(name):
+    _unregister("device_results_model", name)
+
+
 def kernel_name(holder):
     return lib().fabber_vb_kernel_name(C.byref(holder.cfg)).decode()
+
+
+def postproc_kernel_name(holder):
+    """Where postproc_host / postproc_device take model fit and residuals from: "postproc" (a built-in model),
+    "postproc<NAME>" (the kernel a model library compiled around its body), or "" where a request for either image is
+    refused (-85: a library body without a results entry)."""
+    return lib().fabber_vb_postproc_kernel_name(C.byref(holder.cfg)).decode()
 
 
 def nlls_kernel_name(holder):
@@ -372,6 +395,51 @@ def postproc_host(holder, data, mvn, want=("mean", "var", "std", "zstat", "model
         setattr(pp, k, arrs[k].ctypes.data)
     _check(lib().fabber_vb_postproc_host(C.byref(cfg), data.ctypes.data, mvn.ctypes.data, C.byref(pp), device))
     return arrs
+
+
+def postproc_device(holder, data, mvn, want=("mean", "var", "std", "zstat", "modelfit", "residuals", "noise_mean", "noise_std"),
+                    stream=None):
+    """fabber_vb_postproc_device: the result images from device memory. data [T][V] (float32 or float64) and mvn
+    [mvn_rows][V] (float64) are contiguous torch tensors on one device; the holder's design matrix, constants block and
+    parameter table are uploaded next to them. Enqueued on `stream` (default: torch's current); returns the images as
+    torch tensors on that device (read them after synchronising)."""
+    import torch
+    cfg = holder.cfg
+    V, T, P, N = cfg.n_voxels, cfg.n_times, cfg.n_params, holder.n_noise_outputs
+    assert data.is_cuda and data.is_contiguous() and data.dtype in (torch.float32, torch.float64) and tuple(data.shape) == (T, V)
+    assert mvn.is_cuda and mvn.is_contiguous() and mvn.dtype == torch.float64 and tuple(mvn.shape) == (holder.n_mvn_rows, V)
+    dev = data.device
+    d = vbabi.FvbConfig.from_buffer_copy(cfg)
+    d.data_f64 = 1 if data.dtype == torch.float64 else 0
+    keep = []
+
+    def up(arr):
+        keep.append(torch.from_numpy(np.ascontiguousarray(arr)).to(dev))
+        return keep[-1].data_ptr()
+    if "design" in holder.keep:
+        d.design = up(holder.keep["design"])
+    if "constants" in holder.keep:
+        d.model_consts = up(holder.keep["constants"])
+    if cfg.params_ext:  # (the table itself is device memory too; the result images read its transforms only)
+        tab = holder.keep["param_table"][0]
+        ext = vbabi.FvbParamTable()
+        for f, a in tab.items():
+            if f != "image_prior":
+                setattr(ext, f, up(a))
+        d.params_ext = up(np.frombuffer(bytes(ext), dtype=np.uint8))
+    shapes = dict(mean=(P, V), var=(P, V), std=(P, V), zstat=(P, V), modelfit=(T, V), residuals=(T, V),
+                  noise_mean=(N, V), noise_std=(N, V))
+    pp = vbabi.FvbPostproc()
+    out = {}
+    for k in want:
+        out[k] = torch.full(shapes[k], float("nan"), dtype=torch.float64, device=dev)
+        setattr(pp, k, out[k].data_ptr())
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    _check(lib().fabber_vb_postproc_device(C.byref(d), data.data_ptr(), mvn.data_ptr(), C.byref(pp), C.c_void_p(stream.cuda_stream)))
+    for t in keep:  # (the uploads are freed in the order of the stream the kernel reads them on)
+        t.record_stream(stream)
+    return out
 
 
 def convergence_trace(conv, F, max_iterations=10, max_trials=10, min_fchange=0.01, stop_at_done=True):

@@ -115,6 +115,14 @@ class FvbDeviceSpatialModel(C.Structure):
                 ("state_rows", C.c_int32), ("launch", LAUNCH_FN)]
 
 
+class FvbDeviceResultsModel(C.Structure):
+    """fvb_device_results_model: the result-image kernel (model fit and residuals) of a device body, any parameter count
+    (include/fabber_device_results_model.h)"""
+    LAUNCH_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32)
+    _fields_ = [("name", C.c_char_p), ("abi_version", C.c_int32), ("config_size", C.c_uint32), ("postproc_size", C.c_uint32),
+                ("launch", LAUNCH_FN)]
+
+
 class FvbOutputs(C.Structure):
     _fields_ = [
         ("mvn", C.c_void_p),

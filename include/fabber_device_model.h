@@ -27,9 +27,11 @@
  *
  * a.consts / a.n_consts are the model's constants (a list of inversion times, a dose, a TR): read-only device memory,
  * the same for every voxel, filled from DeviceModelSpec::constants (fvb_config.model_consts). The expression must be
- * the one the model's host EvaluateModel computes - the host code still provides the initial posterior, the result
- * images, and the whole fit wherever the device body is not used (spatial VB, the host-model option, and method=nlls
- * unless the library also uses the macros of fabber_device_nlls_model.h).
+ * the one the model's host EvaluateModel computes - the host code still provides the initial posterior, the extra
+ * outputs of save-model-extras, model fit and residuals unless the library also uses the macro of
+ * fabber_device_results_model.h, and the whole fit wherever the device body is not used (the host-model option, spatial
+ * VB unless the library also uses the macro of fabber_device_spatial_model.h, and method=nlls unless it uses those of
+ * fabber_device_nlls_model.h).
  *
  * The macro, at namespace scope, once per model:
  *   - instantiates the white-noise kernel (with and without the free energy) and the four AR(1) kernels for the body;
@@ -49,7 +51,9 @@
  * The lane-per-voxel kernels (one voxel per lane: the engine's throughput kernels, for white noise with one precision
  * from a few thousand voxels up) are compiled around the same body by fabber_device_lane_model.h, one macro line per
  * parameter count, next to the line above. The NLLS minimisers of method=nlls (one wavefront or one lane per voxel, the
- * whole minimisation in one launch) are compiled around it by fabber_device_nlls_model.h in the same way.
+ * whole minimisation in one launch) are compiled around it by fabber_device_nlls_model.h in the same way, the two
+ * kernels of spatial VB that evaluate the model by fabber_device_spatial_model.h, and the result-image kernel (model fit
+ * and residuals) by fabber_device_results_model.h.
  */
 #ifndef FABBER_DEVICE_MODEL_H
 #define FABBER_DEVICE_MODEL_H

@@ -334,11 +334,47 @@ typedef struct fvb_summary
 int32_t fabber_vb_run_host_multi(const fvb_config *cfg, const void *data, const fvb_outputs *out,
     const int32_t *devices, int32_t n_devices, fvb_summary *summary);
 
-/* Result images from the packed MVN (device pointers, asynchronous on stream). */
+/* Result images from the packed MVN (device pointers, asynchronous on stream). Means, variances and noise images need
+ * no model. modelfit / residuals of a built-in model come from the engine's own kernel; of a device body of a model
+ * library (FVB_MODEL_PLUGIN) from the kernel its library compiled around the body (the registry below), and without such
+ * an entry the call answers -85 - it never writes images the engine cannot compute. */
 int32_t fabber_vb_postproc_device(const fvb_config *cfg, const void *data, const double *mvn,
     const fvb_postproc *pp, void *stream);
+/* The same with HOST pointers (cfg->design, cfg->model_consts, the table of cfg->params_ext included). */
 int32_t fabber_vb_postproc_host(const fvb_config *cfg, const void *data, const double *mvn,
     const fvb_postproc *pp, int32_t device);
+
+/*
+ * The result-image kernel for a device body of a model library (FABBER_DEVICE_RESULTS_MODEL in
+ * include/fabber_device_results_model.h): a fifth, independent registry keyed by the name alone - the kernel takes any
+ * parameter count. An entry is used only next to a body of the same name in the registry of
+ * fabber_vb_register_device_model. `launch` receives what fabber_vb_postproc_device received (device pointers; cfg and pp
+ * are passed to the kernel by value, sizeof = config_size / postproc_size) and the number of noise entries of the MVN that
+ * have images; it works out the grid, launches asynchronously on `stream` (a hipStream_t) and returns 0 or a negative code
+ * with its message in err. Registration is refused with -80 (descriptor, name or launcher NULL, name too long), -81
+ * (another ABI version), -82 (another sizeof(fvb_config) or sizeof(fvb_postproc)) or -83 (duplicate name); unregistering a
+ * name that is not there answers -84. The lifetime rules are those of fabber_vb_register_device_model.
+ */
+typedef int32_t (*fvb_device_results_launch_fn)(const fvb_config *cfg, const void *data, const double *mvn, const fvb_postproc *pp,
+                                                int32_t n_noise, void *stream, char *err, int32_t err_len);
+typedef struct fvb_device_results_model
+{
+    const char *name;
+    int32_t abi_version;    /* FVB_ABI_VERSION the library was compiled against */
+    uint32_t config_size;   /* sizeof(fvb_config) */
+    uint32_t postproc_size; /* sizeof(fvb_postproc) */
+    fvb_device_results_launch_fn launch;
+} fvb_device_results_model;
+int32_t fabber_vb_register_device_results_model(const fvb_device_results_model *model);
+int32_t fabber_vb_unregister_device_results_model(const char *name);
+int32_t fabber_vb_device_results_model_count(void);
+const char *fabber_vb_device_results_model_name(int32_t i); /* NULL when i is out of range */
+
+/* Where fabber_vb_postproc_* would take the model fit and the residuals of a configuration from: "postproc" (a built-in
+ * model: the engine's kernel), "postproc<NAME>" (the kernel of a library's results entry), "" where a call that asks for
+ * either image answers -85 (a library body without a results entry) or the configuration is refused. Reads what
+ * fabber_vb_postproc_device validates. */
+const char *fabber_vb_postproc_kernel_name(const fvb_config *cfg);
 
 /*
  * Spatial VB (Vb::DoCalculationsSpatial, inference_vb.cc:578-767; SpatialPrior, priors.cc:183-488;
