@@ -74,6 +74,34 @@ template <> struct DeviceRegistryTraits<fvb_device_lane_model>
         return "no lane kernels of a device model '" + name + "' with " + std::to_string(n_params) + " parameters are registered";
     }
 };
+// ... and their lane-per-voxel kernels under AR(1) noise and noise patterns (include/fabber_device_lane_noise_model.h), by
+// (name, parameter count): a registry of its own, an entry says which of the two families its library compiled.
+template <> struct DeviceRegistryTraits<fvb_device_lane_noise_model>
+{
+    static constexpr const char *noun = "device lane noise model", *is = "are";
+    static constexpr int first_code = -70;
+    static std::vector<DeviceStructSize> sizes(const fvb_device_lane_noise_model &m)
+    {
+        return { { "KernelArgs", m.kernel_args_size, sizeof(KernelArgs) } };
+    }
+    static const char *bad_params(const fvb_device_lane_noise_model &m)
+    {
+        if (m.n_params < 1 || m.n_params > 6)
+            return "the lane kernels of a library body exist for 1 to 6";
+        if (m.families == 0 || (m.families & ~(FVB_LANE_NOISE_AR1 | FVB_LANE_NOISE_PHIS)) != 0)
+            return "the families mask names none of FVB_LANE_NOISE_AR1 and FVB_LANE_NOISE_PHIS, or a family this engine does not know";
+        return (m.save_rows_ar1 < 0 || m.save_rows_phis2 < 0 || m.save_rows_phis4 < 0) ? "a negative row count of the save buffer" : nullptr;
+    }
+    static std::string entry(const std::string &name, int n_params)
+    {
+        return "AR(1) / noise-pattern lane kernels of a device model named '" + name + "' with " + std::to_string(n_params) + " parameters";
+    }
+    static std::string absent(const std::string &name, int n_params)
+    {
+        return "no AR(1) / noise-pattern lane kernels of a device model '" + name + "' with " + std::to_string(n_params)
+            + " parameters are registered";
+    }
+};
 // ... and the result-image kernel of such bodies (include/fabber_device_results_model.h), by name: the kernel takes any
 // parameter count. Looked into only for a name the first registry holds.
 template <> struct DeviceRegistryTraits<fvb_device_results_model>
@@ -115,7 +143,7 @@ int fail(int code, const std::string &msg)
     return code;
 }
 
-thread_local std::string g_kernel_name; // fabber_vb_kernel_name of a registered body: "wave<NAME>", "lane<NAME,P>"
+thread_local std::string g_kernel_name; // fabber_vb_kernel_name of a registered body: "wave<NAME>", "lane<NAME,P>", "lane_ar1<NAME,P>", ...
 
 int validate(const fvb_config *cfg, bool allow_spatial = false, bool allow_no_noise = false)
 {
@@ -185,14 +213,24 @@ int validate(const fvb_config *cfg, bool allow_spatial = false, bool allow_no_no
 constexpr int WAVE_KERNEL_BELOW_VOXELS = 4096;
 
 // The lane kernels a configuration runs on: the engine's own (k) or, for a body from a model library, the ones its
-// library compiled (launch: the library's launcher; of k only save_rows is set). Neither: the wave-per-voxel kernels.
+// library compiled (launch: the library's launcher, white noise with one precision; noise_launch: the one of its AR(1) and
+// noise-pattern kernels, with the family and, for a pattern, the moment sets N of the kernel; of k only save_rows is
+// set). Neither: the wave-per-voxel kernels.
 struct LaneRoute
 {
     LaneKernelInfo k{ nullptr, 0, nullptr };
     fvb_device_lane_launch_fn launch = nullptr;
+    fvb_device_lane_noise_launch_fn noise_launch = nullptr;
+    int family = 0, pattern_n = 0;
+    // the feeds the route has kernels for: the caller's image in place, the tiled series
+    bool has_strided = false, has_tiles = false;
     bool any() const
     {
-        return k.fn || k.fn_tiles_f32 || launch;
+        return has_strided || has_tiles;
+    }
+    bool library() const
+    {
+        return launch || noise_launch;
     }
 };
 
@@ -285,19 +323,45 @@ LaneRoute select_lane(const fvb_config *cfg)
     if (cfg->model != FVB_MODEL_PLUGIN)
     {
         route.k = select_builtin_lane(cfg);
+        route.has_strided = route.k.fn != nullptr;
+        route.has_tiles = route.k.fn_tiles_f32 != nullptr;
         return route;
     }
-    // A body from a model library: its lane kernels exist for white noise with one precision and for the parameter
-    // counts its library registered; the wave-per-voxel kernels of the body take everything else (a body's evaluation
-    // is counted once in the size rule).
-    if (g_variant == 2 || cfg->noise != FVB_NOISE_WHITE || cfg->n_phis != 1
-        || !lane_worth_it(cfg, (double)cfg->n_times * (2 * cfg->n_params + 1)))
+    // A body from a model library: its lane kernels exist for the parameter counts and the noise models its library
+    // registered; the wave-per-voxel kernels of the body take everything else (a body's evaluation is counted once in
+    // the size rule).
+    if (g_variant == 2)
         return route;
-    fvb_device_lane_model entry;
-    if (DeviceRegistry<fvb_device_lane_model>::instance().find(config_device_model(cfg), cfg->n_params, &entry))
+    const double evaluations = (double)cfg->n_times * (2 * cfg->n_params + 1);
+    if (cfg->noise == FVB_NOISE_WHITE && cfg->n_phis == 1) // include/fabber_device_lane_model.h: all three feeds
     {
-        route.launch = entry.launch;
-        route.k.save_rows = entry.save_rows;
+        fvb_device_lane_model entry;
+        if (lane_worth_it(cfg, evaluations) && DeviceRegistry<fvb_device_lane_model>::instance().find(config_device_model(cfg), cfg->n_params, &entry))
+        {
+            route.launch = entry.launch;
+            route.k.save_rows = entry.save_rows;
+            route.has_strided = route.has_tiles = true;
+        }
+        return route;
+    }
+    // include/fabber_device_lane_noise_model.h, under the conditions select_builtin_lane places on the built-in kernels
+    // of the family: AR(1) with one echo (no size rule, tiles only), 2 to 4 precisions (the class bytes fit LDS, the
+    // size rule; the series in place only). Two echoes and 5 to 8 precisions: the wave kernels.
+    const bool ar1 = cfg->noise == FVB_NOISE_AR1 && cfg->n_phis == 1;
+    const bool phis = cfg->noise == FVB_NOISE_WHITE && cfg->n_phis >= 2 && cfg->n_phis <= 4;
+    if (!ar1 && !(phis && cfg->n_times <= 32768 && lane_worth_it(cfg, evaluations)))
+        return route;
+    fvb_device_lane_noise_model entry;
+    const int family = ar1 ? FVB_LANE_NOISE_AR1 : FVB_LANE_NOISE_PHIS;
+    if (DeviceRegistry<fvb_device_lane_noise_model>::instance().find(config_device_model(cfg), cfg->n_params, &entry)
+        && (entry.families & family) != 0)
+    {
+        route.noise_launch = entry.launch;
+        route.family = family;
+        route.pattern_n = ar1 ? 0 : (cfg->n_phis == 2 ? 2 : 4);
+        route.k.save_rows = ar1 ? entry.save_rows_ar1 : (route.pattern_n == 2 ? entry.save_rows_phis2 : entry.save_rows_phis4);
+        route.has_tiles = ar1;
+        route.has_strided = !ar1;
     }
     return route;
 }
@@ -677,6 +741,36 @@ int32_t fabber_vb_device_lane_model_params(int32_t i)
     return DeviceRegistry<fvb_device_lane_model>::instance().params(i, 0);
 }
 
+int32_t fabber_vb_register_device_lane_noise_model(const fvb_device_lane_noise_model *model)
+{
+    return DeviceRegistry<fvb_device_lane_noise_model>::instance().add(model);
+}
+
+int32_t fabber_vb_unregister_device_lane_noise_model(const char *name, int32_t n_params)
+{
+    return DeviceRegistry<fvb_device_lane_noise_model>::instance().remove(name, n_params);
+}
+
+int32_t fabber_vb_device_lane_noise_model_count(void)
+{
+    return DeviceRegistry<fvb_device_lane_noise_model>::instance().count();
+}
+
+const char *fabber_vb_device_lane_noise_model_name(int32_t i)
+{
+    return DeviceRegistry<fvb_device_lane_noise_model>::instance().name(i);
+}
+
+int32_t fabber_vb_device_lane_noise_model_params(int32_t i)
+{
+    return DeviceRegistry<fvb_device_lane_noise_model>::instance().params(i, 0);
+}
+
+int32_t fabber_vb_find_device_lane_noise_model(const char *name, int32_t n_params, fvb_device_lane_noise_model *entry)
+{
+    return (name && entry && DeviceRegistry<fvb_device_lane_noise_model>::instance().find(name, n_params, entry)) ? 1 : 0;
+}
+
 const char *fabber_vb_kernel_name(const fvb_config *cfg)
 {
     if (validate(cfg) != 0)
@@ -684,8 +778,14 @@ const char *fabber_vb_kernel_name(const fvb_config *cfg)
     const LaneRoute route = select_lane(cfg);
     if (cfg->model == FVB_MODEL_PLUGIN)
     {
-        g_kernel_name = route.launch ? "lane<" + config_device_model(cfg) + "," + std::to_string(cfg->n_params) + (cfg->need_f ? ",F>" : ">")
-                                     : "wave<" + config_device_model(cfg) + ">";
+        // (the built-in spellings with the body's name in them)
+        const std::string of = "<" + config_device_model(cfg) + "," + std::to_string(cfg->n_params);
+        if (route.family == FVB_LANE_NOISE_PHIS)
+            g_kernel_name = "lane_phis" + of + "," + std::to_string(route.pattern_n) + ">";
+        else if (route.library())
+            g_kernel_name = (route.family == FVB_LANE_NOISE_AR1 ? "lane_ar1" : "lane") + of + (cfg->need_f ? ",F>" : ">");
+        else
+            g_kernel_name = "wave<" + config_device_model(cfg) + ">";
         return g_kernel_name.c_str();
     }
     if (route.any() && g_variant != 2)
@@ -747,8 +847,7 @@ int run_device_as(const fvb_config *cfg, const void *data, const fvb_outputs *ou
     choice.n_voxels = kernel_voxels;
     const LaneRoute route = select_lane(&choice);
     const LaneKernelInfo &lk = route.k;
-    // (a library's lane kernels: all three feeds, as FVB_LANE_CASE instantiates them)
-    const bool has_strided = lk.fn || route.launch, has_tiles = lk.fn_tiles_f32 || route.launch;
+    const bool has_strided = route.has_strided, has_tiles = route.has_tiles;
     auto work_alloc = [&](void **p, size_t bytes) { return slot ? slot->take(p, bytes) : api_pool_alloc(p, bytes, stream); };
     if (route.any())
     {
@@ -781,11 +880,13 @@ int run_device_as(const fvb_config *cfg, const void *data, const fvb_outputs *ou
         // (the several-precisions kernels keep the T class bytes of the noise pattern in dynamic LDS)
         const size_t lds = (cfg->noise == FVB_NOISE_WHITE && cfg->n_phis > 1) ? (size_t)((cfg->n_times + 15) & ~15) : 0;
         const bool counting = cfg->convergence == FVB_CONV_MAXITS;
-        if (route.launch) // the kernels live in the library's code object: its launcher starts the one for this feed
+        if (route.library()) // the kernels live in the library's code object: its launcher starts the one for this feed
         {
             char msg[512];
             msg[0] = 0;
-            rc = route.launch(&ka, feed, counting ? 1 : 0, (void *)stream, msg, (int32_t)sizeof(msg));
+            // (the class bytes of a pattern kernel are sized here and nowhere else: the count travels in the call)
+            rc = route.noise_launch ? route.noise_launch(&ka, route.family, route.pattern_n, feed, (uint32_t)lds, (void *)stream, msg, (int32_t)sizeof(msg))
+                                    : route.launch(&ka, feed, counting ? 1 : 0, (void *)stream, msg, (int32_t)sizeof(msg));
             if (rc)
                 g_last_error = msg;
         }

@@ -20,6 +20,7 @@ _LIB = None
 # spell it, the descriptor class, and whether an entry's key carries a parameter count next to the name
 _DEVICE_ENTRIES = (("device_model", vbabi.FvbDeviceModel, False),
                    ("device_lane_model", vbabi.FvbDeviceLaneModel, True),
+                   ("device_lane_noise_model", vbabi.FvbDeviceLaneNoiseModel, True),
                    ("device_nlls_model", vbabi.FvbDeviceNllsModel, True),
                    ("device_spatial_model", vbabi.FvbDeviceSpatialModel, True),
                    ("device_results_model", vbabi.FvbDeviceResultsModel, False))
@@ -94,6 +95,8 @@ def lib():
             if keyed:
                 fn("KIND_params").restype = C.c_int32
                 fn("KIND_params").argtypes = [C.c_int32]
+        L.fabber_vb_find_device_lane_noise_model.restype = C.c_int32
+        L.fabber_vb_find_device_lane_noise_model.argtypes = [C.c_char_p, C.c_int32, C.POINTER(vbabi.FvbDeviceLaneNoiseModel)]
         L.fabber_nlls_kernel_name.restype = C.c_char_p
         L.fabber_nlls_kernel_name.argtypes = [cfgp]
         L.fabber_vb_spatial_kernel_name.restype = C.c_char_p
@@ -152,7 +155,7 @@ def device_models():
 
 def register_device_model(descriptor):
     """fabber_vb_register_device_model with a vbabi.FvbDeviceModel (the caller keeps it alive); raises with the engine's
-    message when the registration is refused. The four below: the same with the descriptor class of their kind."""
+    message when the registration is refused. The five below: the same with the descriptor class of their kind."""
     _register("device_model", descriptor)
 
 
@@ -171,6 +174,26 @@ def register_device_lane_model(descriptor):
 
 def unregister_device_lane_model(name, n_params):
     _unregister("device_lane_model", name, n_params)
+
+
+def device_lane_noise_models():
+    """(name, parameter count) of the AR(1) / noise-pattern lane-kernel entries registered with the engine
+    (include/fabber_device_lane_noise_model.h)."""
+    return _listed("device_lane_noise_model", True)
+
+
+def register_device_lane_noise_model(descriptor):
+    _register("device_lane_noise_model", descriptor)
+
+
+def unregister_device_lane_noise_model(name, n_params):
+    _unregister("device_lane_noise_model", name, n_params)
+
+
+def find_device_lane_noise_model(name, n_params):
+    """a copy of the entry for (name, n_params) - families, rows of the save buffers, launcher - or None"""
+    entry = vbabi.FvbDeviceLaneNoiseModel()
+    return entry if lib().fabber_vb_find_device_lane_noise_model(name.encode(), n_params, C.byref(entry)) else None
 
 
 def device_nlls_models():

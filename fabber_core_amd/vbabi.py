@@ -99,6 +99,19 @@ class FvbDeviceLaneModel(C.Structure):
                 ("save_rows", C.c_int32), ("launch", LAUNCH_FN)]
 
 
+LANE_NOISE_AR1, LANE_NOISE_PHIS = 1, 2  # FVB_LANE_NOISE_*: the kernel families of a FvbDeviceLaneNoiseModel
+
+
+class FvbDeviceLaneNoiseModel(C.Structure):
+    """fvb_device_lane_noise_model: the lane-per-voxel kernels of a device body under AR(1) noise and noise patterns for one
+    parameter count (include/fabber_device_lane_noise_model.h); launch(kernel_args, family, pattern_n, feed, lds_bytes,
+    stream, err, err_len)"""
+    LAUNCH_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32)
+    _fields_ = [("name", C.c_char_p), ("abi_version", C.c_int32), ("kernel_args_size", C.c_uint32), ("n_params", C.c_int32),
+                ("families", C.c_int32), ("save_rows_ar1", C.c_int32), ("save_rows_phis2", C.c_int32), ("save_rows_phis4", C.c_int32),
+                ("launch", LAUNCH_FN)]
+
+
 class FvbDeviceNllsModel(C.Structure):
     """fvb_device_nlls_model: an NLLS minimiser of a device body - n_params = 0 the wave-per-voxel one, 1 to 6 the
     lane-per-voxel one for that parameter count (include/fabber_device_nlls_model.h)"""

@@ -24,9 +24,11 @@
  *
  * The engine takes the lane route for a configuration when a lane entry for (name, n_params) is registered, the noise
  * is white with one precision, the kernel variant is not `wave`, and the size rule of the built-in models holds (variant
- * `lane`, or at least 4096 voxels, or fewer than 400 model evaluations per pass). Everything else - noise patterns,
- * AR(1) noise, other parameter counts, small volumes - runs the wave kernels of FABBER_DEVICE_MODEL. The body is
- * evaluated pointwise, as in the wave kernels (a library cannot supply a sweep), and the kernel's name is
+ * `lane`, or at least 4096 voxels, or fewer than 400 model evaluations per pass). AR(1) noise with one echo and noise
+ * patterns of 2 to 4 precisions have lane kernels of their own, which a library compiles with a line of
+ * fabber_device_lane_noise_model.h (FABBER_DEVICE_LANE_NOISE_MODEL); without that line they run the wave kernels of
+ * FABBER_DEVICE_MODEL, as everything else does - two echoes, 5 to 8 precisions, other parameter counts, small volumes.
+ * The body is evaluated pointwise, as in the wave kernels (a library cannot supply a sweep), and the kernel's name is
  * lane<NAME,P> / lane<NAME,P,F>.
  *
  * The macro, at namespace scope:

@@ -267,8 +267,8 @@ const char *fabber_vb_device_model_name(int32_t i); /* NULL when i is out of ran
 /*
  * The lane-per-voxel kernels for such a body (FABBER_DEVICE_LANE_MODEL in include/fabber_device_lane_model.h): a second,
  * independent registry keyed by (name, n_params), 1 <= n_params <= 6. An entry is used only next to a body of the same
- * name in the registry above, which stays the route for everything the lane kernels of a library do not cover (noise
- * patterns, AR(1), other parameter counts, small volumes). The engine sets up the work buffers and the series feed as
+ * name in the registry above, which stays the route for everything the lane kernels of a library do not cover (other
+ * parameter counts, small volumes; noise patterns and AR(1) unless the library registered the entry further down). The engine sets up the work buffers and the series feed as
  * for a built-in model and `launch` starts the kernel for them: feed 0 = the caller's [t][voxel] image read in place,
  * 1 = float tiles, 2 = double tiles; counting != 0 = the run's detector only counts iterations (tile feeds with the
  * free energy). save_rows is the number of rows of the save buffer the kernels with an F-driven detector need. The
@@ -290,6 +290,44 @@ int32_t fabber_vb_unregister_device_lane_model(const char *name, int32_t n_param
 int32_t fabber_vb_device_lane_model_count(void);
 const char *fabber_vb_device_lane_model_name(int32_t i); /* NULL when i is out of range */
 int32_t fabber_vb_device_lane_model_params(int32_t i);   /* 0 when i is out of range */
+
+/*
+ * The lane-per-voxel kernels for such a body under AR(1) noise and under a noise pattern (FABBER_DEVICE_LANE_NOISE_MODEL in
+ * include/fabber_device_lane_noise_model.h): a third registry keyed by (name, n_params), 1 <= n_params <= 6, independent
+ * of the one above (an entry needs a body of its name, not a white-noise lane entry). `families` says which kernels the
+ * library compiled: FVB_LANE_NOISE_AR1 = AR(1) noise with one echo (float and double tiles, with and without the free
+ * energy; no in-place feed: AR(1) refuses masked timepoints), FVB_LANE_NOISE_PHIS = 2 to 4 precisions (the series read in
+ * place; a kernel with 2 and one with 4 moment sets, the free energy a run-time switch). Two echoes, cross terms and 5 to 8
+ * precisions stay on the wave kernels. save_rows_*: the rows of the save buffer of the family's kernels, 0 for a family
+ * that is absent. `launch` receives the family (one FVB_LANE_NOISE_* bit), for a pattern the moment sets of the kernel
+ * (2 or 4; 0 for AR(1)), the feed as above, and the dynamic LDS bytes of the launch as the engine worked them out (the
+ * pattern kernels keep one class byte per timepoint there: a launcher passes the count on and never computes one); it
+ * answers -40 with its message for a family it was not compiled with and for a feed the family has no kernel for. The
+ * refusals and the lifetime rules are those of fabber_vb_register_device_lane_model.
+ */
+#define FVB_LANE_NOISE_AR1 1
+#define FVB_LANE_NOISE_PHIS 2
+typedef int32_t (*fvb_device_lane_noise_launch_fn)(const void *kernel_args, int32_t family, int32_t pattern_n, int32_t feed,
+                                                   uint32_t lds_bytes, void *stream, char *err, int32_t err_len);
+typedef struct fvb_device_lane_noise_model
+{
+    const char *name;
+    int32_t abi_version;       /* FVB_ABI_VERSION the library was compiled against */
+    uint32_t kernel_args_size; /* sizeof(fvb::KernelArgs) */
+    int32_t n_params;
+    int32_t families;          /* FVB_LANE_NOISE_AR1 | FVB_LANE_NOISE_PHIS: not empty */
+    int32_t save_rows_ar1;     /* lane_ar_save_rows<P>() */
+    int32_t save_rows_phis2;   /* lane_pattern_save_rows<P, 2>() */
+    int32_t save_rows_phis4;   /* lane_pattern_save_rows<P, 4>() */
+    fvb_device_lane_noise_launch_fn launch;
+} fvb_device_lane_noise_model;
+int32_t fabber_vb_register_device_lane_noise_model(const fvb_device_lane_noise_model *model);
+int32_t fabber_vb_unregister_device_lane_noise_model(const char *name, int32_t n_params);
+int32_t fabber_vb_device_lane_noise_model_count(void);
+const char *fabber_vb_device_lane_noise_model_name(int32_t i); /* NULL when i is out of range */
+int32_t fabber_vb_device_lane_noise_model_params(int32_t i);   /* 0 when i is out of range */
+/* A copy of the entry for (name, n_params) in *entry - its mask, its row counts, its launcher - and 1; 0 without one. */
+int32_t fabber_vb_find_device_lane_noise_model(const char *name, int32_t n_params, fvb_device_lane_noise_model *entry);
 
 /* Which kernel a configuration would dispatch to ("lane<exp,4>" / "wave" / "wave<NAME>" for a registered body ...). */
 const char *fabber_vb_kernel_name(const fvb_config *cfg);
