@@ -732,6 +732,22 @@ void Vb::DoCalculations(FabberRunData &rundata)
         LOG << "Vb::Model evaluations on " << nthreads << " host thread(s)" << endl;
         series = engine_series(rundata, true, cfg.data_f64, series_rows, series_cols);
     };
+    // The initial posterior of a library's device body: where its library compiled the initial-posterior kernel around the
+    // body's init_posterior (include/fabber_device_init_model.h) the engine writes the image itself, on the device, ahead
+    // of the fit; else the model's host code does, one voxel after the other (BuildInitialMvn). A lap of its own either
+    // way, for FVB_HOST_TIMING to tell the two apart.
+    auto library_initial_posterior = [&]() {
+        timer.lap("up to the initial posterior");
+        const string kernel = fabber_vb_init_posterior_kernel_name(&cfg);
+        if (kernel.empty()) // (continue-from-mvn included: the given image is the initial posterior)
+        {
+            BuildInitialMvn(rundata, cfg);
+            timer.lap("initial posterior on the host (one thread)");
+            return;
+        }
+        LOG << "Vb::the initial posterior comes from the body '" << cfg.device_model << "' of its library (kernel " << kernel << ")" << endl;
+        timer.lap("initial posterior left to the engine (kernel on the device)");
+    };
     if (m_locked_linear)
     {
         // In the voxelwise loop the locked centres only serve the set-up re-centre, which the loop
@@ -816,10 +832,11 @@ void Vb::DoCalculations(FabberRunData &rundata)
             if (kernels[0])
             {
                 // the library brought spatial kernels for this parameter count and noise model; they know no model's
-                // InitVoxelPosterior: the initial posterior comes from the model's host code
+                // InitVoxelPosterior: the initial posterior comes from the library's kernel for it, or from the model's
+                // host code
                 LOG << "Vb::the model runs on the device with the body '" << cfg.device_model << "' of its library, kernels "
                     << kernels << endl;
-                BuildInitialMvn(rundata, cfg);
+                library_initial_posterior();
             }
             rc = fabber_vb_run_spatial_host(&cfg, &sp, series, &out, device, spatial_progress);
         }
@@ -862,9 +879,10 @@ void Vb::DoCalculations(FabberRunData &rundata)
     {
         if (m_store->library_device_model)
         {
-            // the kernels know no model's InitVoxelPosterior: the initial posterior comes from the model's host code
+            // the fit kernels know no model's InitVoxelPosterior: the initial posterior comes from the library's kernel for
+            // it, or from the model's host code
             LOG << "Vb::the model runs on the device with the body '" << cfg.device_model << "' of its library" << endl;
-            BuildInitialMvn(rundata, cfg);
+            library_initial_posterior();
         }
         LOG << "Vb::Voxelwise calculations on the MI355X engine, kernel " << fabber_vb_kernel_name(&cfg) << ", "
             << m_nvoxels << " voxels x " << cfg.n_times << " timepoints" << endl;

@@ -125,6 +125,29 @@ template <> struct DeviceRegistryTraits<fvb_device_results_model>
         return "no result-image kernel of a device model '" + name + "' is registered";
     }
 };
+// ... and their initial-posterior kernel (include/fabber_device_init_model.h), by name: any parameter count. Looked into
+// only for a name the first registry holds.
+template <> struct DeviceRegistryTraits<fvb_device_init_model>
+{
+    static constexpr const char *noun = "device init model", *is = "is";
+    static constexpr int first_code = -90;
+    static std::vector<DeviceStructSize> sizes(const fvb_device_init_model &m)
+    {
+        return { { "fvb_config", m.config_size, sizeof(fvb_config) } };
+    }
+    static const char *bad_params(const fvb_device_init_model &)
+    {
+        return nullptr;
+    }
+    static std::string entry(const std::string &name, int)
+    {
+        return "the initial-posterior kernel of a device model named '" + name + "'";
+    }
+    static std::string absent(const std::string &name, int)
+    {
+        return "no initial-posterior kernel of a device model '" + name + "' is registered";
+    }
+};
 } // namespace fvb
 
 namespace
@@ -825,7 +848,12 @@ int run_device_as(const fvb_config *cfg, const void *data, const fvb_outputs *ou
         return fail(-21, "data is NULL");
     if (cfg->noise == FVB_NOISE_AR1 && n_unmasked != cfg->n_times)
         return fail(-15, "Masked time points are not supported for the AR noise model"); // noisemodel_ar.cc:351-355
-    if (cfg->model == FVB_MODEL_PLUGIN && !cfg->init_mvn) // (as for host-evaluated models: the kernels know no model's InitVoxelPosterior)
+    // A library body without init_mvn: the fit kernels know no model's InitVoxelPosterior. The kernel the library compiled
+    // around the body's init_posterior writes the image (include/fabber_device_init_model.h); without such an entry the
+    // image has to come from the model's host code, as for host-evaluated models.
+    fvb_device_init_model init_entry;
+    const bool init_on_device = cfg->model == FVB_MODEL_PLUGIN && !cfg->init_mvn && find_init_entry(cfg, &init_entry);
+    if (cfg->model == FVB_MODEL_PLUGIN && !cfg->init_mvn && !init_on_device)
         return fail(-52, "host-evaluated models need the initial posterior as init_mvn (the model's InitVoxelPosterior runs on the host)");
     api_keep_pool_memory();
     KernelArgs ka;
@@ -849,6 +877,17 @@ int run_device_as(const fvb_config *cfg, const void *data, const fvb_outputs *ou
     const LaneKernelInfo &lk = route.k;
     const bool has_strided = route.has_strided, has_tiles = route.has_tiles;
     auto work_alloc = [&](void **p, size_t bytes) { return slot ? slot->take(p, bytes) : api_pool_alloc(p, bytes, stream); };
+    // (a work buffer like the tiles: the block's slot on the pipelined host path - every block initialises its own columns -
+    // the stream-ordered pool otherwise; written on the run's stream ahead of the kernels that read it)
+    double *init_image = nullptr;
+    if (init_on_device)
+    {
+        const size_t rows = (size_t)fabber_vb_mvn_rows(cfg->n_params + noise_outputs(cfg));
+        FVB_HIP_CHECK(work_alloc((void **)&init_image, sizeof(double) * rows * (size_t)cfg->n_voxels));
+        if ((rc = launch_init_entry(init_entry, cfg, data, init_image, stream)) != 0)
+            return rc;
+        ka.cfg.init_mvn = init_image;
+    }
     if (route.any())
     {
         if (needs_save(cfg))
@@ -894,7 +933,7 @@ int run_device_as(const fvb_config *cfg, const void *data, const fvb_outputs *ou
             rc = launch_lane_kernel(lk, ka, feed, counting, lds, stream, g_last_error);
         if (rc)
             return rc;
-        for (void *work : { tiles, (void *)ka.save })
+        for (void *work : { tiles, (void *)ka.save, (void *)init_image })
             if (work && !slot)
                 FVB_HIP_CHECK(api_pool_free(work, stream));
         return 0;
@@ -907,7 +946,11 @@ int run_device_as(const fvb_config *cfg, const void *data, const fvb_outputs *ou
         char msg[512];
         msg[0] = 0;
         rc = body.launch(&ka, (void *)stream, msg, (int32_t)sizeof(msg));
-        return rc ? fail(rc, msg) : 0;
+        if (rc)
+            return fail(rc, msg);
+        if (init_image && !slot)
+            FVB_HIP_CHECK(api_pool_free(init_image, stream));
+        return 0;
     }
     return launch_wave_kernel(ka, stream, g_last_error);
 }
@@ -1538,6 +1581,97 @@ int32_t fabber_vb_postproc_host(const fvb_config *cfg, const void *data, const d
     for (int i = 0; i < 8; i++)
         if (*items[i].host)
             FVB_HIP_CHECK(hipMemcpy(*items[i].host, *items[i].dev, sizeof(double) * items[i].rows * V, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int32_t fabber_vb_register_device_init_model(const fvb_device_init_model *model)
+{
+    return DeviceRegistry<fvb_device_init_model>::instance().add(model);
+}
+
+int32_t fabber_vb_unregister_device_init_model(const char *name)
+{
+    return DeviceRegistry<fvb_device_init_model>::instance().remove(name, 0);
+}
+
+int32_t fabber_vb_device_init_model_count(void)
+{
+    return DeviceRegistry<fvb_device_init_model>::instance().count();
+}
+
+const char *fabber_vb_device_init_model_name(int32_t i)
+{
+    return DeviceRegistry<fvb_device_init_model>::instance().name(i);
+}
+
+namespace
+{
+thread_local std::string g_init_kernel_name;
+// (the prior types of spatial VB are as good as any other here; a parameter table has none of them)
+int validate_for_init(const fvb_config *cfg)
+{
+    return validate(cfg, !(cfg && cfg->params_ext));
+}
+} // namespace
+
+const char *fabber_vb_init_posterior_kernel_name(const fvb_config *cfg)
+{
+    if (validate_for_init(cfg) != 0 || cfg->init_mvn || !find_init_entry(cfg))
+        return "";
+    g_init_kernel_name = "init<" + config_device_model(cfg) + ">";
+    return g_init_kernel_name.c_str();
+}
+
+int32_t fabber_vb_init_posterior_device(const fvb_config *cfg, const void *data, double *init_mvn_out, void *stream)
+{
+    int rc = validate_for_init(cfg);
+    if (rc)
+        return rc;
+    if (!init_mvn_out)
+        return fail(-22, "the image to write (init_mvn_out) is NULL");
+    if (cfg->model != FVB_MODEL_PLUGIN)
+        return fail(-95, "the initial posterior of a built-in model is set inside its fit kernels: there is no image to compute "
+                         "(fabber_vb_init_posterior_* is for the device body of a model library, FVB_MODEL_PLUGIN)");
+    fvb_device_init_model entry;
+    if (!find_init_entry(cfg, &entry))
+        return fail(-95, "initial posterior of the device model '" + config_device_model(cfg)
+                + "': its library registered no initial-posterior kernel for it (FABBER_DEVICE_INIT_MODEL in "
+                  "include/fabber_device_init_model.h); the model's InitVoxelPosterior runs on the host");
+    if (cfg->n_voxels == 0)
+        return 0;
+    if (!data)
+        return fail(-21, "data is NULL");
+    return launch_init_entry(entry, cfg, data, init_mvn_out, (hipStream_t)stream);
+}
+
+int32_t fabber_vb_init_posterior_host(const fvb_config *cfg, const void *data, double *init_mvn_out, int32_t device)
+{
+    int rc = validate_for_init(cfg);
+    if (rc)
+        return rc;
+    if (cfg->model != FVB_MODEL_PLUGIN || !find_init_entry(cfg)) // (the refusals of the device entry point, before any upload)
+        return fabber_vb_init_posterior_device(cfg, data, init_mvn_out, nullptr);
+    if (!init_mvn_out)
+        return fail(-22, "the image to write (init_mvn_out) is NULL");
+    if (fabber_vb_device_count() <= 0)
+        return fail(-30, "no HIP device available (the VB engine has no CPU fallback)");
+    FVB_HIP_CHECK(hipSetDevice(device));
+    const size_t V = (size_t)cfg->n_voxels;
+    if (V == 0)
+        return 0;
+    if (!data)
+        return fail(-21, "data is NULL");
+    // the series, the constants and the image priors (or the parameter table) go up as for a fit; the staged problem's
+    // result image has the rows of the initial posterior: the kernel writes it there
+    const size_t rows = (size_t)fabber_vb_mvn_rows(cfg->n_params + noise_outputs(cfg));
+    fvb_outputs none;
+    memset(&none, 0, sizeof(none));
+    StagedProblem staged;
+    if ((rc = staged.stage_in(cfg, data, &none, rows, 0, V, nullptr, from_pool(), STAGE_PRIORS)) != 0)
+        return rc;
+    if ((rc = fabber_vb_init_posterior_device(&staged.d, staged.b_data.p, staged.dout.mvn, nullptr)) != 0)
+        return rc;
+    FVB_HIP_CHECK(hipMemcpy(init_mvn_out, staged.dout.mvn, sizeof(double) * rows * V, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -34,9 +34,13 @@ struct DeviceStructSize
 //   absent(name, n_params)      what unregistering an entry that is not there is told
 template <class D> struct DeviceRegistryTraits;
 
-// The key of an entry is (name, parameter count); the descriptors of the wave body and of the result-image kernel have
-// no count: 0
+// The key of an entry is (name, parameter count); the descriptors of the wave body, of the result-image kernel and of
+// the initial-posterior kernel have no count: 0
 inline int registered_params(const fvb_device_model &)
+{
+    return 0;
+}
+inline int registered_params(const fvb_device_init_model &)
 {
     return 0;
 }
@@ -155,6 +159,25 @@ inline bool find_wave_body(const std::string &name, fvb_device_model *entry = nu
 inline std::string config_device_model(const fvb_config *cfg)
 {
     return std::string(cfg->device_model, strnlen(cfg->device_model, sizeof(cfg->device_model)));
+}
+
+// the initial-posterior kernel of the body a configuration names (include/fabber_device_init_model.h): an entry counts
+// next to a wave body of its name
+inline bool find_init_entry(const fvb_config *cfg, fvb_device_init_model *entry = nullptr)
+{
+    if (cfg->model != FVB_MODEL_PLUGIN)
+        return false;
+    const std::string name = config_device_model(cfg);
+    return find_wave_body(name) && DeviceRegistry<fvb_device_init_model>::instance().find(name, 0, entry);
+}
+
+// A run of such a body without cfg->init_mvn: the entry's kernel writes the image into `image` (device memory, the rows
+// of the configuration's MVN) on the run's stream, ahead of everything that reads it. 0, or the code with its message.
+inline int launch_init_entry(const fvb_device_init_model &entry, const fvb_config *cfg, const void *data, double *image, hipStream_t stream)
+{
+    char err[256] = "";
+    const int rc = entry.launch(cfg, data, image, (void *)stream, err, (int32_t)sizeof(err));
+    return rc ? api_fail(rc, "initial-posterior kernel of the device model '" + config_device_model(cfg) + "': " + err) : 0;
 }
 
 // the argument checks of a configuration with FVB_MODEL_PLUGIN

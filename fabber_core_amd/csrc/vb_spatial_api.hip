@@ -189,7 +189,21 @@ int fvb_spatial_run::open(const fvb_config *cfg_, const fvb_spatial *sp_, const 
         library = route.library;
     }
     if (library && !cfg.init_mvn)
-        return api_fail(-52, spatial_init_mvn_refusal);
+    {
+        // the library's initial-posterior kernel (include/fabber_device_init_model.h) writes the image for every local
+        // voxel, on this run's stream: the set-up kernel's stream waits for that stream before it starts (start_setup)
+        fvb_device_init_model init_entry;
+        if (!find_init_entry(&cfg, &init_entry))
+            return api_fail(-52, spatial_init_mvn_refusal);
+        if (V > 0)
+        {
+            FVB_HIP_CHECK(d_init_mvn.alloc(sizeof(double) * (size_t)fabber_vb_mvn_rows(P + noise_outputs(&cfg)) * (size_t)V, stream));
+            const int rc_init = launch_init_entry(init_entry, &cfg, d_data, (double *)d_init_mvn.p, stream);
+            if (rc_init)
+                return rc_init;
+            cfg.init_mvn = (const double *)d_init_mvn.p;
+        }
+    }
     if (cfg.model == FVB_MODEL_HOSTJAC && !lin_next) // (the kernels read the host's linearisations)
         return api_fail(-56, "a model evaluated on the host runs spatial VB through fabber_vb_run_spatial_hostmodel_host");
     noise_lds = k.lds_classes ? (size_t)cfg.n_times : 0;
@@ -1062,7 +1076,7 @@ static int32_t run_spatial_host_impl(const fvb_config *cfg, const fvb_spatial *s
         return api_fail(-44, spatial_noise_refusal);
     if (!spatial_kernels_for(cfg).found())
         return api_fail(-40, spatial_kernels_refusal(cfg));
-    if (cfg->model == FVB_MODEL_PLUGIN && !cfg->init_mvn)
+    if (cfg->model == FVB_MODEL_PLUGIN && !cfg->init_mvn && !find_init_entry(cfg)) // (with an entry: fvb_spatial_run::open)
         return api_fail(-52, spatial_init_mvn_refusal);
     const int P = cfg->n_params;
     const int n = P + noise_outputs(cfg), rows = n * (n + 1) / 2 + n + 1;

@@ -91,6 +91,9 @@ struct fvb_spatial_run
     std::vector<long long> level_value; // the level (weighted co-ordinate sum) of each entry of level_begin
     int level_w[3] = { 1, 1, 1 };
     fvb::DevMem d_state, d_nn, d_nn_dir, d_order, d_aK, d_partials, d_fprior, d_status, d_sa, d_sums, d_seg_start;
+    // the initial posterior of a library body that came without init_mvn, written by the library's initial-posterior
+    // kernel (include/fabber_device_init_model.h); cfg.init_mvn points here then
+    fvb::DevMem d_init_mvn;
     int n_segments = 0;
     double t_geometry_ms = 0, t_neighbours_ms = 0;
     // the split first sweep (vb_spatial.h): whole-volume runs, or one of several slabs that sweep together

@@ -23,7 +23,8 @@ _DEVICE_ENTRIES = (("device_model", vbabi.FvbDeviceModel, False),
                    ("device_lane_noise_model", vbabi.FvbDeviceLaneNoiseModel, True),
                    ("device_nlls_model", vbabi.FvbDeviceNllsModel, True),
                    ("device_spatial_model", vbabi.FvbDeviceSpatialModel, True),
-                   ("device_results_model", vbabi.FvbDeviceResultsModel, False))
+                   ("device_results_model", vbabi.FvbDeviceResultsModel, False),
+                   ("device_init_model", vbabi.FvbDeviceInitModel, False))
 
 
 class HipEngineError(RuntimeError):
@@ -103,6 +104,12 @@ def lib():
         L.fabber_vb_spatial_kernel_name.argtypes = [cfgp]
         L.fabber_vb_postproc_kernel_name.restype = C.c_char_p
         L.fabber_vb_postproc_kernel_name.argtypes = [cfgp]
+        L.fabber_vb_init_posterior_kernel_name.restype = C.c_char_p
+        L.fabber_vb_init_posterior_kernel_name.argtypes = [cfgp]
+        L.fabber_vb_init_posterior_device.restype = C.c_int32
+        L.fabber_vb_init_posterior_device.argtypes = [cfgp, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.fabber_vb_init_posterior_host.restype = C.c_int32
+        L.fabber_vb_init_posterior_host.argtypes = [cfgp, C.c_void_p, C.c_void_p, C.c_int32]
         if L.fabber_vb_abi_version() != vbabi.FVB_ABI_VERSION:
             raise HipEngineError("libfabber_vb_hip.so ABI version mismatch: rebuild")
         _LIB = L
@@ -155,7 +162,7 @@ def device_models():
 
 def register_device_model(descriptor):
     """fabber_vb_register_device_model with a vbabi.FvbDeviceModel (the caller keeps it alive); raises with the engine's
-    message when the registration is refused. The five below: the same with the descriptor class of their kind."""
+    message when the registration is refused. The six below: the same with the descriptor class of their kind."""
     _register("device_model", descriptor)
 
 
@@ -234,6 +241,24 @@ def register_device_results_model(descriptor):
 
 def unregister_device_results_model(name):
     _unregister("device_results_model", name)
+
+
+def device_init_models():
+    """Names of the initial-posterior kernels registered with the engine (include/fabber_device_init_model.h)."""
+    return _listed("device_init_model", False)
+
+
+def register_device_init_model(descriptor):
+    _register("device_init_model", descriptor)
+
+
+def unregister_device_init_model(name):
+    _unregister("device_init_model", name)
+
+
+def find_device_init_model(name):
+    """True where an initial-posterior kernel of that name is registered (it is used next to a wave body of the name)"""
+    return name in device_init_models()
 
 
 def kernel_name(holder):
@@ -463,6 +488,72 @@ def postproc_device(holder, data, mvn, want=("mean", "var", "std", "zstat", "mod
     for t in keep:  # (the uploads are freed in the order of the stream the kernel reads them on)
         t.record_stream(stream)
     return out
+
+
+def device_config(holder, dev, f64):
+    """A copy of the holder's configuration whose pointer members are DEVICE memory on the torch device `dev` - design
+    matrix, constants block, noise pattern, image priors, the parameter table with its images, init_mvn - for the entry
+    points that take device pointers. f64: the element type of the series the call will be given. Returns (config, the
+    tensors that hold the uploads): keep the second alive until the work that reads them is over."""
+    import torch
+    d = vbabi.FvbConfig.from_buffer_copy(holder.cfg)
+    d.data_f64 = 1 if f64 else 0
+    keep = []
+
+    def up(arr):
+        keep.append(torch.from_numpy(np.ascontiguousarray(arr)).to(dev))
+        return keep[-1].data_ptr()
+    for field, key in (("design", "design"), ("model_consts", "constants"), ("phi_index", "phi_index"), ("init_mvn", "init_mvn")):
+        if key in holder.keep:
+            setattr(d, field, up(holder.keep[key]))
+    images = {k: up(holder.keep["image_%d" % k]) for k in range(d.n_params) if "image_%d" % k in holder.keep}
+    if d.params_ext:  # (the table itself is device memory too, and so is its list of image pointers)
+        tab = holder.keep["param_table"][0]
+        ext = vbabi.FvbParamTable()
+        for f, a in tab.items():
+            if f == "image_prior":
+                a = np.array([images.get(k, 0) for k in range(d.n_params)], dtype=np.int64)  # (pointers; torch has no uint64)
+            setattr(ext, f, up(a))
+        d.params_ext = up(np.frombuffer(bytearray(bytes(ext)), dtype=np.uint8))
+    else:
+        for k, p in images.items():
+            d.image_prior[k] = p
+    return d, keep
+
+
+def init_posterior_kernel_name(holder):
+    """The kernel that writes the initial posterior of a configuration without init_mvn: "init<NAME>" (the kernel a model
+    library compiled around its body's init_posterior, include/fabber_device_init_model.h), or "" - a built-in model, a
+    library body without an init entry (a run without init_mvn answers -52), a given init_mvn, a refused configuration."""
+    return lib().fabber_vb_init_posterior_kernel_name(C.byref(holder.cfg)).decode()
+
+
+def init_posterior_host(holder, data, device=0):
+    """fabber_vb_init_posterior_host: the initial posterior image [mvn_rows][V] of a library body with an init entry, from
+    host arrays (-95 for a body without one and for a built-in model)."""
+    data = _prepare_data(holder, data)
+    img = np.full((holder.n_mvn_rows, holder.cfg.n_voxels), np.nan)
+    _check(lib().fabber_vb_init_posterior_host(C.byref(holder.cfg), data.ctypes.data, img.ctypes.data, device))
+    return img
+
+
+def init_posterior_device(holder, data, stream=None):
+    """fabber_vb_init_posterior_device: the same from device memory. data [T][V] (float32 or float64) is a contiguous torch
+    tensor on a GPU; the holder's constants block, image priors and parameter table are uploaded next to it. Enqueued on
+    `stream` (default: torch's current); returns the image as a torch tensor on that device (read it after
+    synchronising)."""
+    import torch
+    cfg = holder.cfg
+    V, T = cfg.n_voxels, cfg.n_times
+    assert data.is_cuda and data.is_contiguous() and data.dtype in (torch.float32, torch.float64) and tuple(data.shape) == (T, V)
+    d, keep = device_config(holder, data.device, data.dtype == torch.float64)
+    img = torch.full((holder.n_mvn_rows, V), float("nan"), dtype=torch.float64, device=data.device)
+    if stream is None:
+        stream = torch.cuda.current_stream(data.device)
+    _check(lib().fabber_vb_init_posterior_device(C.byref(d), data.data_ptr(), img.data_ptr(), C.c_void_p(stream.cuda_stream)))
+    for t in keep:  # (the uploads are freed in the order of the stream the kernel reads them on)
+        t.record_stream(stream)
+    return img
 
 
 def convergence_trace(conv, F, max_iterations=10, max_trials=10, min_fchange=0.01, stop_at_done=True):

@@ -136,6 +136,13 @@ class FvbDeviceResultsModel(C.Structure):
                 ("launch", LAUNCH_FN)]
 
 
+class FvbDeviceInitModel(C.Structure):
+    """fvb_device_init_model: the initial-posterior kernel of a device body, any parameter count
+    (include/fabber_device_init_model.h)"""
+    LAUNCH_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32)
+    _fields_ = [("name", C.c_char_p), ("abi_version", C.c_int32), ("config_size", C.c_uint32), ("launch", LAUNCH_FN)]
+
+
 class FvbOutputs(C.Structure):
     _fields_ = [
         ("mvn", C.c_void_p),
@@ -270,7 +277,7 @@ def build_config(model, n_voxels, n_times, *, degree=None, design=None, num_exps
     MODEL_PLUGIN (a device body registered by a model library, hiplib.load_model_library): device_model = its
     registered name, constants = what the body reads as ModelArgs::consts, params = the model's parameter defaults
     (as model_parameter_defaults returns them); num_exps and dt travel as model_iopt[0] / model_dopt[0]. Such a
-    model needs init_mvn.
+    model needs init_mvn unless its library registered an init entry for it (hiplib.init_posterior_kernel_name).
 
     param_overrides: {name: dict(type=, mean=, prec=, transform=)} == PSP_byname options
     (fwdmodel.cc:238-266). image_priors: {name: float64 array [n_voxels]}.

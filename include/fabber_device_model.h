@@ -27,9 +27,9 @@
  *
  * a.consts / a.n_consts are the model's constants (a list of inversion times, a dose, a TR): read-only device memory,
  * the same for every voxel, filled from DeviceModelSpec::constants (fvb_config.model_consts). The expression must be
- * the one the model's host EvaluateModel computes - the host code still provides the initial posterior, the extra
- * outputs of save-model-extras, model fit and residuals unless the library also uses the macro of
- * fabber_device_results_model.h, and the whole fit wherever the device body is not used (the host-model option, spatial
+ * the one the model's host EvaluateModel computes - the host code still provides the initial posterior unless the
+ * library also uses the macro of fabber_device_init_model.h, the extra outputs of save-model-extras, model fit and
+ * residuals unless the library also uses the macro of fabber_device_results_model.h, and the whole fit wherever the device body is not used (the host-model option, spatial
  * VB unless the library also uses the macro of fabber_device_spatial_model.h, and method=nlls unless it uses those of
  * fabber_device_nlls_model.h).
  *
@@ -53,7 +53,8 @@
  * parameter count, next to the line above. The NLLS minimisers of method=nlls (one wavefront or one lane per voxel, the
  * whole minimisation in one launch) are compiled around it by fabber_device_nlls_model.h in the same way, the two
  * kernels of spatial VB that evaluate the model by fabber_device_spatial_model.h, and the result-image kernel (model fit
- * and residuals) by fabber_device_results_model.h.
+ * and residuals) by fabber_device_results_model.h, and the initial-posterior kernel - around one more member of the body,
+ * init_posterior - by fabber_device_init_model.h.
  */
 #ifndef FABBER_DEVICE_MODEL_H
 #define FABBER_DEVICE_MODEL_H

@@ -22,7 +22,8 @@
  * the body (FVB_MODEL_PLUGIN) - fabber_vb_postproc_kernel_name says "postproc<NAME>" - and method=vb, spatialvb and nlls
  * take the two images from there, also where the fit itself ran on the model's host code (a library without spatial
  * kernels or minimisers). Without one the engine refuses such a request (-85) and the host code provides the images, as
- * it does with the host-model option. The initial posterior and save-model-extras stay host code.
+ * it does with the host-model option. save-model-extras stays host code; the initial posterior too, without the macro
+ * of fabber_device_init_model.h.
  *
  * The macro, at namespace scope, once per model:
  *   - instantiates the kernel for the body, for up to FVB_MAX_PARAMS and up to FVB_MAX_PARAMS_EXT parameters;

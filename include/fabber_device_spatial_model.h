@@ -22,8 +22,9 @@
  * The engine takes these kernels for a configuration when an entry for (name, n_params) is registered and the noise is
  * white with one precision; the kernel table's name is spatial<NAME,P>. Noise patterns, AR(1) noise, other parameter
  * counts and a volume cut into z-slabs over several devices keep the host route (-40 from the engine, after which
- * method=spatialvb evaluates the model's host code as before). The initial posterior comes from the host (init_mvn): the
- * kernels know no library's InitVoxelPosterior. The body is evaluated pointwise, as in the lane kernels.
+ * method=spatialvb evaluates the model's host code as before). The initial posterior is an image (init_mvn): these
+ * kernels know no library's InitVoxelPosterior. It comes from the model's host code, or - where the library also uses the
+ * macro of fabber_device_init_model.h - from the kernel the engine launches ahead of the set-up kernel. The body is evaluated pointwise, as in the lane kernels.
  *
  * The macro, at namespace scope:
  *   - instantiates five kernels for the body: the set-up kernel and the second sweep with and without the free energy,

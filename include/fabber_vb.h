@@ -170,7 +170,8 @@ typedef struct fvb_config
     double min_fchange;   /* also max-fchange for LM */
 
     /* ---- resume (inference_vb.cc:183-216) ---- */
-    const double *init_mvn; /* [n_mvn_rows][n_voxels] continue-from-mvn, or NULL */
+    const double *init_mvn; /* [n_mvn_rows][n_voxels] continue-from-mvn, or NULL (FVB_MODEL_PLUGIN: NULL answers -52
+                               unless the body has an init entry, fabber_vb_register_device_init_model) */
 
     /* ---- output control ---- */
     int32_t f_history_rows; /* 0 = do not record (save-free-energy-history) */
@@ -415,6 +416,51 @@ const char *fabber_vb_device_results_model_name(int32_t i); /* NULL when i is ou
 const char *fabber_vb_postproc_kernel_name(const fvb_config *cfg);
 
 /*
+ * The initial-posterior kernel for a device body of a model library (FABBER_DEVICE_INIT_MODEL in
+ * include/fabber_device_init_model.h): a sixth, independent registry keyed by the name alone - the kernel takes any
+ * parameter count. An entry is used only next to a body of the same name in the registry of
+ * fabber_vb_register_device_model. `launch` receives a validated configuration (device pointers; cfg is passed to the
+ * kernel by value, sizeof = config_size), the series [n_times][n_voxels] and the image to write,
+ * [fabber_vb_mvn_rows(n_params + noise entries)][n_voxels]; it works out the grid, launches asynchronously on `stream`
+ * (a hipStream_t) and returns 0 or a negative code with its message in err. Registration is refused with -90 (descriptor,
+ * name or launcher NULL, name too long), -91 (another ABI version), -92 (another sizeof(fvb_config)) or -93 (duplicate
+ * name); unregistering a name that is not there answers -94. The lifetime rules are those of
+ * fabber_vb_register_device_model.
+ *
+ * With an entry, the entry points that fit a configuration with FVB_MODEL_PLUGIN (fabber_vb_run_device / _run_host /
+ * _run_host_multi, fabber_vb_run_spatial_* and the stepwise spatial functions) no longer need cfg->init_mvn: where it is
+ * NULL the kernel writes the image into a work buffer of the run, on the run's stream, ahead of the fit - every block of
+ * a run cut into blocks initialises its own columns. A given init_mvn always wins. Without an entry such a call answers
+ * -52 as before.
+ */
+typedef int32_t (*fvb_device_init_launch_fn)(const fvb_config *cfg, const void *data, double *init_mvn, void *stream, char *err,
+                                             int32_t err_len);
+typedef struct fvb_device_init_model
+{
+    const char *name;
+    int32_t abi_version;  /* FVB_ABI_VERSION the library was compiled against */
+    uint32_t config_size; /* sizeof(fvb_config) */
+    fvb_device_init_launch_fn launch;
+} fvb_device_init_model;
+int32_t fabber_vb_register_device_init_model(const fvb_device_init_model *model);
+int32_t fabber_vb_unregister_device_init_model(const char *name);
+int32_t fabber_vb_device_init_model_count(void);
+const char *fabber_vb_device_init_model_name(int32_t i); /* NULL when i is out of range */
+
+/* The kernel that writes the initial posterior of a configuration where cfg->init_mvn is NULL: "init<NAME>" (a library
+ * body with an init entry), "" otherwise - a built-in model (its fit kernels initialise themselves), a library body
+ * without an entry (the image has to come from the model's host code), a given init_mvn, or a configuration that is
+ * refused. Reads what fabber_vb_run_spatial_* validates. */
+const char *fabber_vb_init_posterior_kernel_name(const fvb_config *cfg);
+
+/* The initial posterior image alone: init_mvn_out [fabber_vb_mvn_rows(n_params + noise entries)][n_voxels] doubles,
+ * every element written; cfg->init_mvn is not read. Device pointers, asynchronous on `stream`. -95 with a message for a
+ * configuration with FVB_MODEL_PLUGIN whose body has no init entry, and for a built-in model. */
+int32_t fabber_vb_init_posterior_device(const fvb_config *cfg, const void *data, double *init_mvn_out, void *stream);
+/* The same with HOST pointers (cfg->model_consts, the image priors, the table of cfg->params_ext included). */
+int32_t fabber_vb_init_posterior_host(const fvb_config *cfg, const void *data, double *init_mvn_out, int32_t device);
+
+/*
  * Spatial VB (Vb::DoCalculationsSpatial, inference_vb.cc:578-767; SpatialPrior, priors.cc:183-488;
  * Vb::CalcNeighbours, inference_vb.cc:830-964). Selected by method=spatialvb or by any prior of
  * type M, m, P, p. White noise only.
@@ -653,7 +699,8 @@ const char *fabber_nlls_kernel_name(const fvb_config *cfg);
  * around its body and the engine keeps everything else (a_K, the first sweep in both forms, pack). With an entry next to
  * a body of the same name in the registry of fabber_vb_register_device_model, fabber_vb_run_spatial_host / _device and
  * fabber_vb_spatial_open accept FVB_MODEL_PLUGIN for that name and parameter count under white noise with one precision
- * (-40 otherwise, as before; -52 without cfg->init_mvn: the kernels know no library's InitVoxelPosterior). `launch`
+ * (-40 otherwise, as before; -52 without cfg->init_mvn unless the library registered an init entry for the name,
+ * fabber_vb_register_device_init_model: the spatial kernels themselves know no library's InitVoxelPosterior). `launch`
  * receives which kernel to start (FVB_SPATIAL_KERNEL_*), need_f, the engine's arguments (fvb::SpatialArgs, sizeof =
  * spatial_args_size), the grid size in 64-lane workgroups and the dynamic LDS bytes as the engine worked them out; it
  * launches asynchronously on `stream` (a hipStream_t) and returns 0 or a negative code with its message in err.
