@@ -51,6 +51,7 @@ struct DeviceModelSpec
 {
     DeviceModelSpec()
         : model(-1)
+        , uses_suppdata(false)
     {
         for (int i = 0; i < 4; i++)
         {
@@ -67,6 +68,10 @@ struct DeviceModelSpec
      * VB when the name is registered; everywhere else the model is evaluated on the host. */
     std::string device_model;
     std::vector<double> constants;
+    /** Such a body reads the voxel's supplementary data (the `suppdata` option, what EvaluateModel finds in
+     * FwdModel::suppdata) through fvb::supp_at: the engine then hands it the run's supplementary data, all rows.
+     * Spatial VB does not: there such a model is evaluated on the host. */
+    bool uses_suppdata;
 };
 
 class FwdModel : public Loggable

@@ -16,6 +16,7 @@
 using namespace std;
 
 const void *engine_series(FabberRunData &rundata, bool as_matrix, int32_t &data_f64, int &rows, int &cols); // inference_vb.cc
+void engine_suppdata(FabberRunData &rundata, fvb_config &cfg);                                                    // inference_vb.cc
 using NEWMAT::Matrix;
 
 struct NLLSInferenceTechnique::EngineStorage
@@ -146,6 +147,8 @@ void NLLSInferenceTechnique::DoCalculations(FabberRunData &rundata)
             st.constants = spec.constants;
             cfg.model_consts = st.constants.empty() ? NULL : st.constants.data();
             cfg.n_model_consts = (int32_t)st.constants.size();
+            if (spec.uses_suppdata)
+                engine_suppdata(rundata, cfg);
             st.library_device_model = fabber_nlls_kernel_name(&cfg)[0] != 0;
         }
         if (st.library_device_model)
@@ -155,6 +158,8 @@ void NLLSInferenceTechnique::DoCalculations(FabberRunData &rundata)
             memset(cfg.device_model, 0, sizeof(cfg.device_model));
             cfg.model_consts = NULL;
             cfg.n_model_consts = 0;
+            cfg.model_supp = NULL;
+            cfg.n_model_supp = 0;
             device_model = false;
         }
     }
@@ -241,6 +246,8 @@ void NLLSInferenceTechnique::DoCalculations(FabberRunData &rundata)
         if (st.library_device_model)
             LOG << "NLLSInferenceTechnique::the model runs on the device with the body '" << cfg.device_model << "' of its library, kernel "
                 << fabber_nlls_kernel_name(&cfg) << endl;
+        if (st.library_device_model && spec.uses_suppdata)
+            LOG << "NLLSInferenceTechnique::the body receives " << cfg.n_model_supp << " rows of supplementary data" << endl;
         rc = fabber_nlls_run_host(&cfg, &nl, series, &out, device);
     }
     else

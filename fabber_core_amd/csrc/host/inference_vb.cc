@@ -111,6 +111,7 @@ struct Vb::EngineStorage
     bool has_device_model;
     bool library_device_model;     // ... and it is a body the model's library registered (FVB_MODEL_PLUGIN)
     std::vector<double> constants; // its constants (fvb_config.model_consts)
+    bool uses_suppdata;            // ... and it reads the voxels' supplementary data (fvb_config.model_supp)
     // more than FVB_MAX_PARAMS parameters: the per-parameter entries as a table (fvb_config.params_ext)
     vector<int32_t> wide_transform, wide_type;
     vector<double> wide_mean, wide_var, wide_prec, wide_post_mean, wide_post_var;
@@ -240,6 +241,18 @@ const void *engine_series(FabberRunData &rundata, bool as_matrix, int32_t &data_
     return data.Store();
 }
 
+// The run's supplementary data as a library's device body reads it (DeviceModelSpec::uses_suppdata): the matrix is
+// timepoints x voxels with the voxel fastest, which is the engine's layout, so its store is handed over as it is - the
+// run data keeps it for the run. Without one value per voxel there is none (NULL, 0 rows): the body's own bound check
+// then stops every voxel with the non-finite-offset status, as with too few constants.
+void engine_suppdata(FabberRunData &rundata, fvb_config &cfg)
+{
+    const Matrix &supp = rundata.GetVoxelSuppData();
+    const bool per_voxel = cfg.n_voxels > 0 && supp.Ncols() == cfg.n_voxels && supp.Nrows() > 0;
+    cfg.model_supp = per_voxel ? supp.Store() : NULL;
+    cfg.n_model_supp = per_voxel ? supp.Nrows() : 0;
+}
+
 void Vb::BuildEngineConfig(FabberRunData &rundata, fvb_config &cfg)
 {
     EngineStorage &st = *m_store;
@@ -303,7 +316,10 @@ void Vb::BuildEngineConfig(FabberRunData &rundata, fvb_config &cfg)
         st.constants = spec.constants;
         cfg.model_consts = st.constants.empty() ? NULL : st.constants.data();
         cfg.n_model_consts = (int32_t)st.constants.size();
+        if (spec.uses_suppdata)
+            engine_suppdata(rundata, cfg);
     }
+    st.uses_suppdata = st.library_device_model && spec.uses_suppdata;
     cfg.model = spec.model;
     for (int i = 0; i < 4; i++)
     {
@@ -844,10 +860,15 @@ void Vb::DoCalculations(FabberRunData &rundata)
         {
             // no spatial kernels were built for this model with this many parameters: the model's own host code
             // does the re-centres instead (up to 32 parameters; more than 8 under white noise with one precision)
-            LOG << "Vb::no device kernels for spatial VB with " << cfg.n_params << " parameters of this model" << endl;
+            if (m_store->uses_suppdata && cfg.n_model_supp > 0)
+                LOG << "Vb::the spatial kernels hand a body no supplementary data: the model runs on the host route" << endl;
+            else
+                LOG << "Vb::no device kernels for spatial VB with " << cfg.n_params << " parameters of this model" << endl;
             m_store->has_device_model = m_store->library_device_model = false;
             cfg.model = FVB_MODEL_HOSTJAC;
             cfg.design = NULL;
+            cfg.model_supp = NULL;
+            cfg.n_model_supp = 0;
         }
         if (!m_store->has_device_model)
         {
@@ -882,6 +903,8 @@ void Vb::DoCalculations(FabberRunData &rundata)
             // the fit kernels know no model's InitVoxelPosterior: the initial posterior comes from the library's kernel for
             // it, or from the model's host code
             LOG << "Vb::the model runs on the device with the body '" << cfg.device_model << "' of its library" << endl;
+            if (m_store->uses_suppdata)
+                LOG << "Vb::the body receives " << cfg.n_model_supp << " rows of supplementary data" << endl;
             library_initial_posterior();
         }
         LOG << "Vb::Voxelwise calculations on the MI355X engine, kernel " << fabber_vb_kernel_name(&cfg) << ", "
@@ -1022,11 +1045,17 @@ void InferenceTechnique::SaveEngineResults(FabberRunData &rundata, const fvb_con
                 constants = spec.constants;
                 named.model_consts = constants.empty() ? NULL : constants.data();
                 named.n_model_consts = (int32_t)constants.size();
+                named.model_supp = NULL;
+                named.n_model_supp = 0;
+                if (spec.uses_suppdata)
+                    engine_suppdata(rundata, named);
                 const string kernel = fabber_vb_postproc_kernel_name(&named);
                 if (kernel.compare(0, 9, "postproc<") == 0)
                 {
                     LOG << "InferenceTechnique::model fit and residuals with the body '" << named.device_model
                         << "' of its library (kernel " << kernel << ")" << endl;
+                    if (spec.uses_suppdata)
+                        LOG << "InferenceTechnique::the body receives " << named.n_model_supp << " rows of supplementary data" << endl;
                     pcfg = named;
                     device_fit = true;
                 }

@@ -1509,7 +1509,7 @@ int32_t fabber_vb_postproc_host(const fvb_config *cfg, const void *data, const d
     const int rows = fabber_vb_mvn_rows(P + N);
     const size_t esz = cfg->data_f64 ? 8 : 4;
     fvb_config d = *cfg;
-    DevMem b_data, b_design, b_consts, b_mvn;
+    DevMem b_data, b_design, b_consts, b_supp, b_mvn;
     DeviceParamTable ptable;
     if (cfg->params_ext)
     {
@@ -1537,6 +1537,13 @@ int32_t fabber_vb_postproc_host(const fvb_config *cfg, const void *data, const d
         if ((rc = upload_array(b_consts, cfg->model_consts, sizeof(double) * (size_t)cfg->n_model_consts, nullptr)) != 0)
             return rc;
         d.model_consts = (const double *)b_consts.p;
+    }
+    d.model_supp = nullptr; // (the same for the voxels' supplementary data, [n_model_supp][V])
+    if (cfg->model == FVB_MODEL_PLUGIN && cfg->model_supp && cfg->n_model_supp > 0)
+    {
+        if ((rc = upload_array(b_supp, cfg->model_supp, sizeof(double) * (size_t)cfg->n_model_supp * V, nullptr)) != 0)
+            return rc;
+        d.model_supp = (const double *)b_supp.p;
     }
     FVB_HIP_CHECK(b_mvn.alloc(sizeof(double) * rows * V));
     {

@@ -190,6 +190,8 @@ inline int check_device_model_config(const fvb_config *cfg)
         return api_fail(-16, "no device model '" + name + "' is registered (fabber_vb_register_device_model)");
     if (cfg->n_model_consts < 0 || (cfg->n_model_consts > 0 && !cfg->model_consts))
         return api_fail(-17, "device model '" + name + "': n_model_consts constants announced but model_consts is NULL");
+    if (cfg->n_model_supp < 0 || (cfg->n_model_supp > 0 && !cfg->model_supp))
+        return api_fail(-17, "device model '" + name + "': n_model_supp rows of supplementary data announced but model_supp is NULL");
     return 0;
 }
 } // namespace fvb

@@ -265,7 +265,7 @@ struct StagedProblem
     fvb_config d;
     fvb_outputs dout;
     size_t V = 0, v0 = 0, Vb = 0, mvn_rows = 0, history_rows = 0;
-    DevMem b_data, b_design, b_consts, b_phi, b_init, b_img[FVB_MAX_PARAMS], b_mvn, b_small, b_hist;
+    DevMem b_data, b_design, b_consts, b_supp, b_phi, b_init, b_img[FVB_MAX_PARAMS], b_mvn, b_small, b_hist;
     // F (8 bytes), history length, status, iterations (4 each) of a voxel: one device buffer, [F][hlen][status][it]
     static constexpr size_t SMALL_BYTES_PER_VOXEL = 8 + 4 + 4 + 4;
     size_t small_bytes = 0;
@@ -301,6 +301,13 @@ struct StagedProblem
             if ((rc = upload_array(b_consts, cfg->model_consts, sizeof(double) * (size_t)cfg->n_model_consts, stream, src)) != 0)
                 return rc;
             d.model_consts = (const double *)b_consts.p;
+        }
+        d.model_supp = nullptr; // (a host pointer; only a library's body reads the device copy)
+        if (cfg->model == FVB_MODEL_PLUGIN && cfg->model_supp && cfg->n_model_supp > 0) // its voxels' supplementary data:
+        {                                                                               // the rows' columns [v0, v1)
+            if ((rc = upload(b_supp, cfg->model_supp, sizeof(double), (size_t)cfg->n_model_supp)) != 0)
+                return rc;
+            d.model_supp = (const double *)b_supp.p;
         }
         if (cfg->phi_index)
         {
@@ -413,7 +420,7 @@ struct StagedProblem
     // (pool memory goes back in its stream's order: for an owner that destroys that stream itself)
     void release()
     {
-        for (DevMem *m : { &b_data, &b_design, &b_consts, &b_phi, &b_init, &b_mvn, &b_small, &b_hist, &ptable.block })
+        for (DevMem *m : { &b_data, &b_design, &b_consts, &b_supp, &b_phi, &b_init, &b_mvn, &b_small, &b_hist, &ptable.block })
             m->reset();
         for (DevMem &m : b_img)
             m.reset();

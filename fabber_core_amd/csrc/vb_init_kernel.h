@@ -76,6 +76,7 @@ __global__ __launch_bounds__(256) void vb_init_posterior_kernel(const InitArgs i
     ma.exp_table = nullptr;
     ma.consts = ia.cfg.model_consts;
     ma.n_consts = ia.cfg.n_model_consts;
+    set_model_supp(ma, ia.cfg, v);
     ma.model = ia.cfg.model;
     VoxelSeries y;
     y.column = (const char *)ia.data + (size_t)v * (ia.cfg.data_f64 ? sizeof(double) : sizeof(float));

@@ -561,6 +561,7 @@ __global__ __launch_bounds__(64, lane_waves<P>()) void vb_lane_ar_kernel(const K
     ma.design = ka.cfg.design;
     ma.consts = ka.cfg.model_consts; // read by a model library's body only (include/fabber_device_lane_model.h)
     ma.n_consts = ka.cfg.n_model_consts;
+    set_library_model_supp<Model>(ma, ka.cfg, v);
     ma.model = ka.cfg.model;
 
     VoxelState<P> st;

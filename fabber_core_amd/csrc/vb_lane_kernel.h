@@ -803,6 +803,9 @@ __device__ __forceinline__ double rescue_residual(const KernelArgs &ka, const Mo
         const int src = __ffsll((long long)todo) - 1;
         todo &= todo - 1;
         const int vs = __shfl(v, src);
+        // (every lane evaluates the model for voxel vs, not for its own: a library body's supplementary data is that voxel's)
+        ModelArgs ms = ma;
+        set_library_model_supp<Model>(ms, ka.cfg, vs);
         double tp[P], tp2[P], tp3[P], rden[P], nd[P];
 #pragma unroll
         for (int i = 0; i < P; i++)
@@ -836,7 +839,7 @@ __device__ __forceinline__ double rescue_residual(const KernelArgs &ka, const Mo
                 {
                     const double y = load_data(ka, (size_t)t * V + vs);
                     double g, f2[P], f3[P];
-                    sweep.eval(ma, t, tp, tp2, tp3, g, f2, f3);
+                    sweep.eval(ms, t, tp, tp2, tp3, g, f2, f3);
                     double Jd = 0;
 #pragma unroll
                     for (int i = 0; i < P; i++)
@@ -1028,6 +1031,11 @@ __device__ __forceinline__ double rescue_tiles(const KernelArgs &ka, const Model
         // (the rescued voxel's vectors are the same in every lane: told so, they live in scalar registers - or in the
         // lanes of a spill VGPR - instead of 40 VGPRs, which the kernels that also carry F do not have: there the
         // rescue spilled 22 of them to scratch memory and read them back per timepoint, 15 GB of traffic per launch)
+        // (every lane evaluates the model for the voxel of lane src, not for its own: a library body's supplementary data
+        // is that voxel's)
+        ModelArgs ms = ma;
+        if constexpr (Model::model_id == FVB_MODEL_PLUGIN)
+            set_model_supp(ms, ka.cfg, __builtin_amdgcn_readfirstlane(__shfl(v, src)));
         double tp[P], tp2[P], tp3[P], rden[P], nd[P];
 #pragma unroll
         for (int i = 0; i < P; i++)
@@ -1044,7 +1052,7 @@ __device__ __forceinline__ double rescue_tiles(const KernelArgs &ka, const Model
         {
             const double y = (double)wave_tile[(size_t)(t / G) * 64 * G + (size_t)src * G + (t % G)];
             double g, f2[P], f3[P];
-            sweep.eval(ma, t, tp, tp2, tp3, g, f2, f3);
+            sweep.eval(ms, t, tp, tp2, tp3, g, f2, f3);
             double Jd = 0;
 #pragma unroll
             for (int i = 0; i < P; i++)
@@ -1437,6 +1445,7 @@ __global__ __launch_bounds__(64, lane_waves<P>()) void vb_lane_kernel(const Kern
     ma.design = ka.cfg.design;
     ma.consts = ka.cfg.model_consts; // read by a model library's body only (include/fabber_device_lane_model.h)
     ma.n_consts = ka.cfg.n_model_consts;
+    set_library_model_supp<Model>(ma, ka.cfg, v);
     ma.model = ka.cfg.model;
     // this wavefront's block of the tiled series, and this lane's slot in group 0 of it
     const RAW *wave_tile = (FEED == FEED_STRIDED) ? nullptr : (const RAW *)ka.tiles + (size_t)blockIdx.x * Tile<RAW>::block_elems(T);

@@ -473,6 +473,7 @@ __global__ __launch_bounds__(64, (lane_pattern_waves<P, N>())) void vb_lane_patt
     __syncthreads();
     if (v >= ka.cfg.n_voxels)
         return;
+    set_library_model_supp<Model>(ma, ka.cfg, v); // (after the lanes past the end have left)
 #pragma unroll
     for (int k = 0; k < N; k++)
         nz.count[k] = 0;

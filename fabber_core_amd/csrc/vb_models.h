@@ -54,7 +54,37 @@ struct ModelArgs
     int32_t n_consts;
     // the wave-per-voxel kernels' built-in evaluator (vb_wave_kernel.h): fvb_config.model, for eval_model_runtime
     int32_t model;
+    // a device body from a model library: THIS voxel's supplementary data (fvb_config.model_supp, the reference's
+    // `suppdata`) - element 0 of the voxel's column or NULL, the number of rows, and the distance between two rows
+    // (n_voxels of the launch). Read through supp_at below. The defaults say "no supplementary data".
+    const double *supp = nullptr;
+    int32_t n_supp = 0;
+    size_t supp_stride = 0;
 };
+
+// entry k of the voxel's supplementary data; as with consts, the body checks k < a.n_supp itself
+FVB_HD double supp_at(const ModelArgs &a, int k)
+{
+    return a.supp[(size_t)k * a.supp_stride];
+}
+
+// the three supplementary-data members of `ma` for voxel v of the launch (the voxel the lane or wavefront WORKS on)
+FVB_HD void set_model_supp(ModelArgs &ma, const fvb_config &cfg, int v)
+{
+    ma.n_supp = (cfg.model_supp != nullptr) ? cfg.n_model_supp : 0;
+    ma.supp_stride = (size_t)cfg.n_voxels;
+    ma.supp = (cfg.model_supp != nullptr) ? cfg.model_supp + v : nullptr;
+}
+// ... in a kernel that is a template on the model (Model::model_id): only a library's body reads them, and only its
+// instantiations contain the call. A built-in model's kernel is compiled from the code it was compiled from without
+// them (dead code that the optimiser removes still moved the register allocation of six of the 24 exponential lane
+// kernels: DESIGN.md has the tables).
+template <class Model>
+FVB_HD void set_library_model_supp(ModelArgs &ma, const fvb_config &cfg, int v)
+{
+    if constexpr (Model::model_id == FVB_MODEL_PLUGIN)
+        set_model_supp(ma, cfg, v);
+}
 
 // A "sweep" produces, for t = 0, 1, 2, ... in order, the 2P + 1 predictions the central
 // difference needs: g = f(tp) and f2[i] / f3[i] = f(tp with entry i replaced by tp2[i] / tp3[i]).

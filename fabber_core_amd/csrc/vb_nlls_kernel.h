@@ -59,6 +59,7 @@ __global__ __launch_bounds__(64, 2) void nlls_lane_kernel(const NllsArgs na)
     ma.design = ka.cfg.design;
     ma.consts = ka.cfg.model_consts; // read by a model library's body only (include/fabber_device_nlls_model.h)
     ma.n_consts = ka.cfg.n_model_consts;
+    set_library_model_supp<Model>(ma, ka.cfg, v);
     ma.model = ka.cfg.model;
 
     // starting estimate, Fabber space (inference_nlls.cc:131-132: the means of the 'posterior'
@@ -415,7 +416,7 @@ __global__ __launch_bounds__(64) void nlls_wave_kernel(const NllsArgs na, const 
     cx.sv_prec = false;
     double *sh = cx.sh;
 
-    const ModelArgs ma = wave_model_args(ka);
+    const ModelArgs ma = wave_model_args<Eval>(ka, cx.v);
 
     nlls_wave_stage(ka, cx);
     FVB_WAVE_FOR(i, L.P)

@@ -65,6 +65,7 @@ __global__ __launch_bounds__(256) void vb_postproc_kernel(
         ma.design = cfg.design;
         ma.consts = cfg.model_consts;
         ma.n_consts = cfg.n_model_consts;
+        set_model_supp(ma, cfg, v);
         ma.model = cfg.model;
         for (int t = 0; t < T; t++)
         {

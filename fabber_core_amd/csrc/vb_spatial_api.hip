@@ -128,6 +128,8 @@ static SpatialRoute spatial_kernels_for(const fvb_config *cfg)
     const int kind = spatial_noise_kind(cfg);
     if (kind < 0)
         return SpatialRoute{};
+    if (cfg->model == FVB_MODEL_PLUGIN && cfg->n_model_supp > 0)
+        return SpatialRoute{}; // (the spatial kernels hand a body no supplementary data: the model runs on the host route)
     if (cfg->model == FVB_MODEL_PLUGIN)
         return spatial_route_library(cfg, kind);
     SpatialRoute route;

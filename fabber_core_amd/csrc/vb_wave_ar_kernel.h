@@ -703,7 +703,7 @@ __device__ __forceinline__ void wave_ar_kernel_body(const KernelArgs &ka, const 
     const size_t V = cx.V;
     double *sh = cx.sh;
 
-    const ModelArgs ma = wave_model_args(ka);
+    const ModelArgs ma = wave_model_args<Eval>(ka, cx.v);
 
     FVB_WAVE_FOR(t, T)
     {

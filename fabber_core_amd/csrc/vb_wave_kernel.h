@@ -29,6 +29,7 @@
 #include "vb_lane_kernel.h"
 
 #include <string>
+#include <type_traits>
 
 namespace fvb
 {
@@ -224,7 +225,9 @@ struct BuiltinEval
 };
 
 // the model's side of the kernel arguments, as every wave-per-voxel kernel hands it to its evaluator
-__device__ __forceinline__ ModelArgs wave_model_args(const KernelArgs &ka)
+// (v: the voxel the wavefront works on; its supplementary data only where the evaluator is a library's)
+template <class Eval>
+__device__ __forceinline__ ModelArgs wave_model_args(const KernelArgs &ka, int v)
 {
     ModelArgs ma;
     ma.iopt0 = ka.cfg.model_iopt[0];
@@ -232,6 +235,8 @@ __device__ __forceinline__ ModelArgs wave_model_args(const KernelArgs &ka)
     ma.design = ka.cfg.design;
     ma.consts = ka.cfg.model_consts;
     ma.n_consts = ka.cfg.n_model_consts;
+    if constexpr (!std::is_same<Eval, BuiltinEval>::value)
+        set_model_supp(ma, ka.cfg, v);
     ma.model = ka.cfg.model;
     return ma;
 }
@@ -669,7 +674,7 @@ __device__ __forceinline__ void wave_kernel_body(const KernelArgs &ka, const Wav
     const size_t V = cx.V;
     double *sh = cx.sh;
 
-    const ModelArgs ma = wave_model_args(ka);
+    const ModelArgs ma = wave_model_args<Eval>(ka, cx.v);
 
     // ---- stage the voxel's time series and the noise pattern ----
     FVB_WAVE_FOR(t, T)

@@ -46,6 +46,8 @@ class DeviceProblem:
                 self.cfg.init_mvn = t.data_ptr()
             elif name == "constants":
                 self.cfg.model_consts = t.data_ptr()
+            elif name == "suppdata":
+                self.cfg.model_supp = t.data_ptr()
             elif name.startswith("image_"):
                 self.cfg.image_prior[int(name.split("_")[1])] = t.data_ptr()
         V = cfg.n_voxels

@@ -468,6 +468,8 @@ def postproc_device(holder, data, mvn, want=("mean", "var", "std", "zstat", "mod
         d.design = up(holder.keep["design"])
     if "constants" in holder.keep:
         d.model_consts = up(holder.keep["constants"])
+    if "suppdata" in holder.keep:
+        d.model_supp = up(holder.keep["suppdata"])
     if cfg.params_ext:  # (the table itself is device memory too; the result images read its transforms only)
         tab = holder.keep["param_table"][0]
         ext = vbabi.FvbParamTable()
@@ -503,7 +505,8 @@ def device_config(holder, dev, f64):
     def up(arr):
         keep.append(torch.from_numpy(np.ascontiguousarray(arr)).to(dev))
         return keep[-1].data_ptr()
-    for field, key in (("design", "design"), ("model_consts", "constants"), ("phi_index", "phi_index"), ("init_mvn", "init_mvn")):
+    for field, key in (("design", "design"), ("model_consts", "constants"), ("model_supp", "suppdata"), ("phi_index", "phi_index"),
+                       ("init_mvn", "init_mvn")):
         if key in holder.keep:
             setattr(d, field, up(holder.keep[key]))
     images = {k: up(holder.keep["image_%d" % k]) for k in range(d.n_params) if "image_%d" % k in holder.keep}

@@ -15,7 +15,7 @@ import numpy as np
 FVB_MAX_PARAMS = 32
 FVB_MAX_PHIS = 8
 FVB_MAX_ALPHAS = 4
-FVB_ABI_VERSION = 10
+FVB_ABI_VERSION = 11
 FVB_DEVICE_MODEL_NAME_MAX = 48
 
 MODEL_POLY, MODEL_LINEAR, MODEL_EXP, MODEL_HOSTJAC, MODEL_PLUGIN = 0, 1, 2, 100, 101
@@ -81,6 +81,8 @@ class FvbConfig(C.Structure):
         ("device_model", C.c_char * FVB_DEVICE_MODEL_NAME_MAX),
         ("model_consts", C.c_void_p),
         ("n_model_consts", C.c_int32),
+        ("model_supp", C.c_void_p),
+        ("n_model_supp", C.c_int32),
     ]
 
 
@@ -271,13 +273,15 @@ def build_config(model, n_voxels, n_times, *, degree=None, design=None, num_exps
                  need_f=None, f_history_rows=0, noise_pattern="1", masked_timepoints=(),
                  prior_noise_stddev=-1.0, locked_noise_stdev=-1.0, param_overrides=None,
                  image_priors=None, init_mvn=None, noise=NOISE_WHITE, num_echoes=1, ar_cross_terms="none",
-                 ar_alpha_prior=None, ar_alpha_post=None, device_model=None, constants=None, params=None):
+                 ar_alpha_prior=None, ar_alpha_post=None, device_model=None, constants=None, params=None, suppdata=None):
     """Resolve options into an fvb_config whose pointer members are HOST numpy arrays.
 
     MODEL_PLUGIN (a device body registered by a model library, hiplib.load_model_library): device_model = its
     registered name, constants = what the body reads as ModelArgs::consts, params = the model's parameter defaults
     (as model_parameter_defaults returns them); num_exps and dt travel as model_iopt[0] / model_dopt[0]. Such a
     model needs init_mvn unless its library registered an init entry for it (hiplib.init_posterior_kernel_name).
+    suppdata = the voxels' supplementary data, [n_supp][n_voxels] (the reference's `suppdata` image), what such a body
+    reads through fvb::supp_at; the built-in models ignore it.
 
     param_overrides: {name: dict(type=, mean=, prec=, transform=)} == PSP_byname options
     (fwdmodel.cc:238-266). image_priors: {name: float64 array [n_voxels]}.
@@ -433,6 +437,13 @@ def build_config(model, n_voxels, n_times, *, degree=None, design=None, num_exps
         init_mvn = np.ascontiguousarray(init_mvn, dtype=np.float64)
         keep["init_mvn"] = init_mvn
         cfg.init_mvn = init_mvn.ctypes.data
+    if suppdata is not None:
+        suppdata = np.ascontiguousarray(suppdata, dtype=np.float64)
+        if suppdata.ndim != 2 or suppdata.shape[1] != n_voxels:
+            raise ValueError("suppdata: expected an array [n_supp][%d voxels], got shape %r" % (n_voxels, suppdata.shape))
+        keep["suppdata"] = suppdata
+        cfg.model_supp = suppdata.ctypes.data
+        cfg.n_model_supp = suppdata.shape[0]
     return ConfigHolder(cfg, params, keep)
 
 

@@ -35,10 +35,12 @@
  * InitVoxelPosterior overwrites - WITH THE SAME OPERATIONS IN THE SAME ORDER, comparisons included (a NaN sample is
  * skipped by `x > m` and taken by `!(x <= m)`): the two routes then start from the same bits up to the logarithm of
  * the LOG and FRACTIONAL transforms, which the kernel applies afterwards (FwdModel::ToFabber). a.consts / a.n_consts are
- * the model's constants, as in eval; the hook never reads past them.
+ * the model's constants, as in eval; the hook never reads past them. The voxel's supplementary data (the `suppdata`
+ * option; DeviceModelSpec::uses_suppdata) is there too, as in eval: fvb::supp_at(a, k) for k < a.n_supp, which is 0
+ * where the run has none.
  *
- * What the hook cannot express: the off-diagonal covariances of the parameters (the image has zeros there), the voxel's
- * co-ordinates and its supplementary data. A model whose InitVoxelPosterior needs one of them brings NO init entry: the
+ * What the hook cannot express: the off-diagonal covariances of the parameters (the image has zeros there) and the
+ * voxel's co-ordinates. A model whose InitVoxelPosterior needs one of them brings NO init entry: the
  * engine then answers a fit without init_mvn with -52 as before, and fabber_dorun builds the image from the model's host
  * code as before.
  *

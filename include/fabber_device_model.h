@@ -26,7 +26,30 @@
  *     FABBER_DEVICE_MODEL("invrec", InvRec)
  *
  * a.consts / a.n_consts are the model's constants (a list of inversion times, a dose, a TR): read-only device memory,
- * the same for every voxel, filled from DeviceModelSpec::constants (fvb_config.model_consts). The expression must be
+ * the same for every voxel, filled from DeviceModelSpec::constants (fvb_config.model_consts).
+ *
+ * a.supp / a.n_supp / a.supp_stride are THIS voxel's supplementary data - the `suppdata` option of a run, what the host
+ * class finds in FwdModel::suppdata after PassData: a per-voxel input curve (a voxelwise arterial input function, a
+ * reference curve), a per-voxel B1 or T1 that is not a parameter. Read entry k with the accessor
+ *
+ *     fvb::supp_at(a, k)      // = a.supp[k * a.supp_stride], a double; k = 0 .. a.n_supp - 1
+ *
+ * under the rule of the constants: the engine does not know how many rows a body needs, so the body checks
+ * k < a.n_supp itself and answers a non-finite prediction instead of reading past the block (a.supp is NULL and
+ * a.n_supp 0 where a run has no supplementary data):
+ *
+ *         if (t >= a.n_supp)
+ *             return __builtin_nan("");
+ *         return p[0] * fvb::supp_at(a, t) * exp(-p[1] * double(t) * a.dopt0);
+ *
+ * The rows are read-only device memory laid out [row][voxel] (fvb_config.model_supp, n_model_supp): in the lane kernels
+ * a read is one coalesced 8-byte load per lane, in the wave kernels one load of an address that is the same for the
+ * whole wavefront. The host side asks for them with spec.uses_suppdata = true (DeviceModelSpec); the engine then hands
+ * the body the run's supplementary data, all rows, on every route of this family of headers BUT spatial VB: the kernels
+ * of fabber_device_spatial_model.h hand a body no supplementary data, and method=spatialvb runs such a model on the
+ * host route (the log says so).
+ *
+ * The expression must be
  * the one the model's host EvaluateModel computes - the host code still provides the initial posterior unless the
  * library also uses the macro of fabber_device_init_model.h, the extra outputs of save-model-extras, model fit and
  * residuals unless the library also uses the macro of fabber_device_results_model.h, and the whole fit wherever the device body is not used (the host-model option, spatial

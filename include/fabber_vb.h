@@ -46,7 +46,7 @@ extern "C" {
 #define FVB_MAX_PARAMS_EXT 128 /* with fvb_config.params_ext (the wave-per-voxel kernels; what their LDS holds decides) */
 #define FVB_MAX_PHIS 8
 #define FVB_MAX_ALPHAS 4 /* AR(1) coefficients: 2 + ar_cross_terms (noisemodel_ar.cc:360-377) */
-#define FVB_ABI_VERSION 10
+#define FVB_ABI_VERSION 11
 #define FVB_DEVICE_MODEL_NAME_MAX 48 /* bytes of a registered device-model name, the terminator included */
 
 /* Forward models with a device body (fwdmodel_poly.cc:62, fwdmodel_linear.cc:92,
@@ -203,6 +203,10 @@ typedef struct fvb_config
     const double *model_consts; /* [n_model_consts] constants of the model (a list of inversion times, a dose, a TR ...):
                                    what the body finds in ModelArgs::consts. Same memory space as data; may be NULL. */
     int32_t n_model_consts;
+    const double *model_supp; /* [n_model_supp][n_voxels], voxel fastest: the voxels' supplementary data (the reference's
+                                 `suppdata`, FwdModel::PassData), what the body reads through fvb::supp_at. Same memory
+                                 space as data; may be NULL. Ignored for a built-in model. */
+    int32_t n_model_supp;
 } fvb_config;
 
 /* the per-parameter entries wherever they are (host code) */
