@@ -852,6 +852,8 @@ void Vb::DoCalculations(FabberRunData &rundata)
                 // host code
                 LOG << "Vb::the model runs on the device with the body '" << cfg.device_model << "' of its library, kernels "
                     << kernels << endl;
+                if (m_store->uses_suppdata)
+                    LOG << "Vb::the body receives " << cfg.n_model_supp << " rows of supplementary data" << endl;
                 library_initial_posterior();
             }
             rc = fabber_vb_run_spatial_host(&cfg, &sp, series, &out, device, spatial_progress);
@@ -861,7 +863,8 @@ void Vb::DoCalculations(FabberRunData &rundata)
             // no spatial kernels were built for this model with this many parameters: the model's own host code
             // does the re-centres instead (up to 32 parameters; more than 8 under white noise with one precision)
             if (m_store->uses_suppdata && cfg.n_model_supp > 0)
-                LOG << "Vb::the spatial kernels hand a body no supplementary data: the model runs on the host route" << endl;
+                LOG << "Vb::the model's library has no spatial entry for this parameter count and noise model, so its body is handed "
+                       "no supplementary data under spatial VB: the model runs on the host route" << endl;
             else
                 LOG << "Vb::no device kernels for spatial VB with " << cfg.n_params << " parameters of this model" << endl;
             m_store->has_device_model = m_store->library_device_model = false;

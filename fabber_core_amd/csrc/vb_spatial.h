@@ -386,6 +386,7 @@ __global__ __launch_bounds__(64, lane_waves<P>()) void vb_spatial_setup_kernel(c
     ma.consts = ka.cfg.model_consts; // read by a model library's body only (include/fabber_device_spatial_model.h)
     ma.n_consts = ka.cfg.n_model_consts;
     ma.model = ka.cfg.model;
+    set_library_model_supp<Model>(ma, ka.cfg, v); // (v is final: the lanes past the end and the stopped voxels have left)
     ma.exp_table = ACC ? exp_tab : nullptr;
     VoxelState<P> st;
     Moments<P> mo;
@@ -1417,6 +1418,7 @@ __global__ __launch_bounds__(64, lane_waves<P>()) void vb_spatial_noise_kernel(c
     ma.consts = ka.cfg.model_consts; // read by a model library's body only (include/fabber_device_spatial_model.h)
     ma.n_consts = ka.cfg.n_model_consts;
     ma.model = ka.cfg.model;
+    set_library_model_supp<Model>(ma, ka.cfg, v); // (v is final: the lanes past the end and the stopped voxels have left)
     ma.exp_table = ACC ? exp_tab : nullptr;
     VoxelState<P> st;
     Moments<P> mo;

@@ -59,6 +59,34 @@ template <> struct DeviceRegistryTraits<fvb_device_spatial_model>
         return "no " + entry(name, n_params) + " are registered";
     }
 };
+// ... and the ones compiled around the noise policies beyond white noise with one precision
+// (include/fabber_device_spatial_noise_model.h), by (name, parameter count): a registry of its own, an entry says which
+// families its library compiled.
+template <> struct DeviceRegistryTraits<fvb_device_spatial_noise_model>
+{
+    static constexpr const char *noun = "device spatial noise model", *is = "are";
+    static constexpr int first_code = -65;
+    static std::vector<DeviceStructSize> sizes(const fvb_device_spatial_noise_model &m)
+    {
+        return { { "SpatialArgs", m.spatial_args_size, sizeof(SpatialArgs) } };
+    }
+    static const char *bad_params(const fvb_device_spatial_noise_model &m)
+    {
+        if (m.n_params < 1 || m.n_params > 6)
+            return "the spatial kernels of a library body exist for 1 to 6";
+        if (m.families == 0 || (m.families & ~(FVB_SPATIAL_NOISE_AR1 | FVB_SPATIAL_NOISE_PHIS)) != 0)
+            return "the families mask names none of FVB_SPATIAL_NOISE_AR1 and FVB_SPATIAL_NOISE_PHIS, or a family this engine does not know";
+        return (m.state_rows_ar1 < 0 || m.state_rows_phis2 < 0 || m.state_rows_phis4 < 0) ? "a negative row count of the state image" : nullptr;
+    }
+    static std::string entry(const std::string &name, int n_params)
+    {
+        return "AR(1) / noise-pattern spatial kernels of a device model named '" + name + "' with " + std::to_string(n_params) + " parameters";
+    }
+    static std::string absent(const std::string &name, int n_params)
+    {
+        return "no " + entry(name, n_params) + " are registered";
+    }
+};
 } // namespace fvb
 namespace
 {
@@ -68,10 +96,12 @@ struct SpatialRoute
 {
     SpatialKernels k{};
     fvb_device_spatial_launch_fn library = nullptr;
+    fvb_device_spatial_noise_launch_fn library_noise = nullptr; // ... of its entry for the noise policy `kind`
+    int kind = FVB_SPNZ_WHITE;
     std::string name; // fabber_vb_spatial_kernel_name
     bool found() const
     {
-        return k.setup != nullptr || library != nullptr;
+        return k.setup != nullptr || library != nullptr || library_noise != nullptr;
     }
 };
 thread_local std::string g_spatial_kernel_name;
@@ -79,15 +109,43 @@ thread_local std::string g_spatial_kernel_name;
 
 // A body of a model library: the table of the parameter count with the engine's own kernels wherever the model plays no
 // part - the linear model's table serves, it covers 1 ... 8 parameters - and the three that evaluate the model left to
-// the library's launcher. Nothing (-40) without an entry for (name, P), under another noise model, or for a name without
-// a wave body (which the argument checks answer with -16 before this is asked).
+// the library's launcher. Under a noise pattern of 2 to 4 precisions and under AR(1) noise with one echo the same with the
+// policy's table and the launcher of the library's entry for these policies (spatial_route_library_noise). Nothing (-40)
+// without an entry for (name, P) that covers the noise model, under the other noise models, or for a name without a
+// wave body (which the argument checks answer with -16 before this is asked).
+static SpatialRoute spatial_route_library_noise(const fvb_config *cfg, int kind, const std::string &name)
+{
+    SpatialRoute route;
+    fvb_device_spatial_noise_model entry;
+    if ((kind != FVB_SPNZ_PATTERN2 && kind != FVB_SPNZ_PATTERN4 && kind != FVB_SPNZ_AR1)
+        || !DeviceRegistry<fvb_device_spatial_noise_model>::instance().find(name, cfg->n_params, &entry))
+        return route;
+    const int family = kind == FVB_SPNZ_AR1 ? FVB_SPATIAL_NOISE_AR1 : FVB_SPATIAL_NOISE_PHIS;
+    const int rows = kind == FVB_SPNZ_AR1 ? entry.state_rows_ar1 : (kind == FVB_SPNZ_PATTERN2 ? entry.state_rows_phis2 : entry.state_rows_phis4);
+    if ((entry.families & family) == 0)
+        return route;
+    SpatialKernels k = get_spatial_kernels_nz_linear(cfg->n_params, cfg->need_f != 0, kind);
+    if (!k.setup || k.wave || k.state_rows != rows) // (state_rows: compiled against another layout of the policy's statistics)
+        return route;
+    k.setup = k.noise = k.noise_fast = k.noise_acc = k.noise_fast_acc = nullptr; // the library's
+    static const char *const tag[] = { "", "pattern2", "pattern4", "ar1" };
+    route.name = "spatial<" + name + "," + std::to_string(cfg->n_params) + "," + tag[kind] + ">";
+    k.name = nullptr; // (route.name)
+    route.k = k;
+    route.library_noise = entry.launch;
+    route.kind = kind;
+    return route;
+}
 static SpatialRoute spatial_route_library(const fvb_config *cfg, int kind)
 {
     SpatialRoute route;
     const std::string name = config_device_model(cfg);
     fvb_device_spatial_model entry;
-    if (kind != FVB_SPNZ_WHITE || cfg->params_ext || name.empty() || !find_wave_body(name)
-        || !DeviceRegistry<fvb_device_spatial_model>::instance().find(name, cfg->n_params, &entry))
+    if (cfg->params_ext || name.empty() || !find_wave_body(name))
+        return route;
+    if (kind != FVB_SPNZ_WHITE)
+        return spatial_route_library_noise(cfg, kind, name);
+    if (!DeviceRegistry<fvb_device_spatial_model>::instance().find(name, cfg->n_params, &entry))
         return route;
     SpatialKernels k = get_spatial_kernels_linear(cfg->n_params, cfg->need_f != 0);
     if (!k.setup || k.wave || k.lds_classes || k.state_rows != entry.state_rows) // (state_rows: compiled against another SpLayout)
@@ -128,8 +186,6 @@ static SpatialRoute spatial_kernels_for(const fvb_config *cfg)
     const int kind = spatial_noise_kind(cfg);
     if (kind < 0)
         return SpatialRoute{};
-    if (cfg->model == FVB_MODEL_PLUGIN && cfg->n_model_supp > 0)
-        return SpatialRoute{}; // (the spatial kernels hand a body no supplementary data: the model runs on the host route)
     if (cfg->model == FVB_MODEL_PLUGIN)
         return spatial_route_library(cfg, kind);
     SpatialRoute route;
@@ -189,8 +245,10 @@ int fvb_spatial_run::open(const fvb_config *cfg_, const fvb_spatial *sp_, const 
             return api_fail(-40, spatial_kernels_refusal(&cfg));
         k = route.k;
         library = route.library;
+        library_noise = route.library_noise;
+        library_kind = route.kind;
     }
-    if (library && !cfg.init_mvn)
+    if ((library || library_noise) && !cfg.init_mvn)
     {
         // the library's initial-posterior kernel (include/fabber_device_init_model.h) writes the image for every local
         // voxel, on this run's stream: the set-up kernel's stream waits for that stream before it starts (start_setup)
@@ -287,10 +345,11 @@ int fvb_spatial_run::start_setup(const void *d_data, const fvb_outputs *d_out)
 // in its code object (64-lane workgroups either way)
 int fvb_spatial_run::launch_model_kernel(int which, SpatialKernelFn fn, unsigned grid, size_t lds, hipStream_t on)
 {
-    if (library)
+    if (library || library_noise)
     {
         char err[256] = "";
-        const int rc = library(which, cfg.need_f != 0, &sa, grid, (uint32_t)lds, on, err, (int32_t)sizeof(err));
+        const int rc = library_noise ? library_noise(library_kind, which, cfg.need_f != 0, &sa, grid, (uint32_t)lds, on, err, (int32_t)sizeof(err))
+                                     : library(which, cfg.need_f != 0, &sa, grid, (uint32_t)lds, on, err, (int32_t)sizeof(err));
         return rc ? api_fail(rc, err[0] ? err : "the launcher of a device model's spatial kernels failed") : 0;
     }
     hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, on, sa);
@@ -915,6 +974,36 @@ const char *fabber_vb_device_spatial_model_name(int32_t i)
 int32_t fabber_vb_device_spatial_model_params(int32_t i)
 {
     return DeviceRegistry<fvb_device_spatial_model>::instance().params(i, 0);
+}
+
+int32_t fabber_vb_register_device_spatial_noise_model(const fvb_device_spatial_noise_model *model)
+{
+    return DeviceRegistry<fvb_device_spatial_noise_model>::instance().add(model);
+}
+
+int32_t fabber_vb_unregister_device_spatial_noise_model(const char *name, int32_t n_params)
+{
+    return DeviceRegistry<fvb_device_spatial_noise_model>::instance().remove(name, n_params);
+}
+
+int32_t fabber_vb_device_spatial_noise_model_count(void)
+{
+    return DeviceRegistry<fvb_device_spatial_noise_model>::instance().count();
+}
+
+const char *fabber_vb_device_spatial_noise_model_name(int32_t i)
+{
+    return DeviceRegistry<fvb_device_spatial_noise_model>::instance().name(i);
+}
+
+int32_t fabber_vb_device_spatial_noise_model_params(int32_t i)
+{
+    return DeviceRegistry<fvb_device_spatial_noise_model>::instance().params(i, 0);
+}
+
+int32_t fabber_vb_find_device_spatial_noise_model(const char *name, int32_t n_params, fvb_device_spatial_noise_model *entry)
+{
+    return (name && entry && DeviceRegistry<fvb_device_spatial_noise_model>::instance().find(name, n_params, entry)) ? 1 : 0;
 }
 
 // (the selection function of the run: "" where open() would answer -40 or -44)

@@ -725,6 +725,22 @@ __device__ __forceinline__ const uint8_t *sp_classes(const KernelArgs &ka)
     return sp_class_table;
 }
 
+// What a model library's body reads of `ma` beyond the built-in models' three fields (include/fabber_device_spatial_noise_model.h):
+// the constants and voxel v's supplementary data, v the voxel the lane works on. Only a library's instantiations contain
+// the assignments: the built-in models' kernels are compiled from the code they were compiled from without them (see
+// set_library_model_supp).
+template <class Model>
+__device__ __forceinline__ void sp_library_model_args(ModelArgs &ma, const fvb_config &cfg, int v)
+{
+    if constexpr (Model::model_id == FVB_MODEL_PLUGIN)
+    {
+        ma.consts = cfg.model_consts;
+        ma.n_consts = cfg.n_model_consts;
+        ma.model = cfg.model;
+        set_model_supp(ma, cfg, v);
+    }
+}
+
 // ---- setup: Vb::SetupPerVoxelDists (inference_vb.cc:207-247) -----------------------------------------------
 template <class Model, int P, class NZ>
 __global__ __launch_bounds__(64, NZ::WAVES) void vb_spatial_setup_nz_kernel(const SpatialArgs sa)
@@ -741,6 +757,7 @@ __global__ __launch_bounds__(64, NZ::WAVES) void vb_spatial_setup_nz_kernel(cons
     ma.iopt0 = ka.cfg.model_iopt[0];
     ma.dopt0 = ka.cfg.model_dopt[0];
     ma.design = ka.cfg.design;
+    sp_library_model_args<Model>(ma, ka.cfg, v);
     VoxelState<P> st;
     Moments<P> mo;
     typename NZ::Full full;
@@ -829,6 +846,7 @@ __global__ __launch_bounds__(64, NZ::WAVES) void vb_spatial_noise_nz_kernel(cons
     ma.iopt0 = ka.cfg.model_iopt[0];
     ma.dopt0 = ka.cfg.model_dopt[0];
     ma.design = ka.cfg.design;
+    sp_library_model_args<Model>(ma, ka.cfg, v);
     VoxelState<P> st;
     Moments<P> mo;
     sp_load<P>(sa, v, st, mo); // (the effective moments)

@@ -82,6 +82,9 @@ struct fvb_spatial_run
     // that evaluate the model - set-up and the second sweep in its two forms - are the library's then and k's slots for
     // them are NULL; everything else in k is the engine's own for the parameter count
     fvb_device_spatial_launch_fn library = nullptr;
+    // ... or, under a noise pattern or AR(1) noise, of its entry for these policies, which is told the noise kind
+    fvb_device_spatial_noise_launch_fn library_noise = nullptr;
+    int library_kind = 0;
     fvb::SpatialArgs sa;
     hipStream_t stream = nullptr;
     int V = 0, P = 0, owned_begin = 0, owned_end = 0;

@@ -23,6 +23,7 @@ _DEVICE_ENTRIES = (("device_model", vbabi.FvbDeviceModel, False),
                    ("device_lane_noise_model", vbabi.FvbDeviceLaneNoiseModel, True),
                    ("device_nlls_model", vbabi.FvbDeviceNllsModel, True),
                    ("device_spatial_model", vbabi.FvbDeviceSpatialModel, True),
+                   ("device_spatial_noise_model", vbabi.FvbDeviceSpatialNoiseModel, True),
                    ("device_results_model", vbabi.FvbDeviceResultsModel, False),
                    ("device_init_model", vbabi.FvbDeviceInitModel, False))
 
@@ -98,6 +99,8 @@ def lib():
                 fn("KIND_params").argtypes = [C.c_int32]
         L.fabber_vb_find_device_lane_noise_model.restype = C.c_int32
         L.fabber_vb_find_device_lane_noise_model.argtypes = [C.c_char_p, C.c_int32, C.POINTER(vbabi.FvbDeviceLaneNoiseModel)]
+        L.fabber_vb_find_device_spatial_noise_model.restype = C.c_int32
+        L.fabber_vb_find_device_spatial_noise_model.argtypes = [C.c_char_p, C.c_int32, C.POINTER(vbabi.FvbDeviceSpatialNoiseModel)]
         L.fabber_nlls_kernel_name.restype = C.c_char_p
         L.fabber_nlls_kernel_name.argtypes = [cfgp]
         L.fabber_vb_spatial_kernel_name.restype = C.c_char_p
@@ -228,6 +231,26 @@ def register_device_spatial_model(descriptor):
 
 def unregister_device_spatial_model(name, n_params):
     _unregister("device_spatial_model", name, n_params)
+
+
+def device_spatial_noise_models():
+    """(name, parameter count) of the AR(1) / noise-pattern spatial-VB entries registered with the engine
+    (include/fabber_device_spatial_noise_model.h)."""
+    return _listed("device_spatial_noise_model", True)
+
+
+def register_device_spatial_noise_model(descriptor):
+    _register("device_spatial_noise_model", descriptor)
+
+
+def unregister_device_spatial_noise_model(name, n_params):
+    _unregister("device_spatial_noise_model", name, n_params)
+
+
+def find_device_spatial_noise_model(name, n_params):
+    """a copy of the entry for (name, n_params) - families, rows of the state images, launcher - or None"""
+    entry = vbabi.FvbDeviceSpatialNoiseModel()
+    return entry if lib().fabber_vb_find_device_spatial_noise_model(name.encode(), n_params, C.byref(entry)) else None
 
 
 def device_results_models():

@@ -130,6 +130,22 @@ class FvbDeviceSpatialModel(C.Structure):
                 ("state_rows", C.c_int32), ("launch", LAUNCH_FN)]
 
 
+SPATIAL_NOISE_AR1, SPATIAL_NOISE_PHIS = 1, 2  # FVB_SPATIAL_NOISE_*: the kernel families of a FvbDeviceSpatialNoiseModel
+# the engine's number of a noise policy of the spatial kernels, as a FvbDeviceSpatialNoiseModel's launcher is told it
+SPNZ_WHITE, SPNZ_PATTERN2, SPNZ_PATTERN4, SPNZ_AR1 = 0, 1, 2, 3
+
+
+class FvbDeviceSpatialNoiseModel(C.Structure):
+    """fvb_device_spatial_noise_model: the spatial VB kernels of a device body under AR(1) noise and noise patterns for one
+    parameter count (include/fabber_device_spatial_noise_model.h); launch(kind, which, need_f, spatial_args, grid,
+    lds_bytes, stream, err, err_len)"""
+    LAUNCH_FN = C.CFUNCTYPE(C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                            C.c_int32)
+    _fields_ = [("name", C.c_char_p), ("abi_version", C.c_int32), ("spatial_args_size", C.c_uint32), ("n_params", C.c_int32),
+                ("families", C.c_int32), ("state_rows_ar1", C.c_int32), ("state_rows_phis2", C.c_int32), ("state_rows_phis4", C.c_int32),
+                ("launch", LAUNCH_FN)]
+
+
 class FvbDeviceResultsModel(C.Structure):
     """fvb_device_results_model: the result-image kernel (model fit and residuals) of a device body, any parameter count
     (include/fabber_device_results_model.h)"""

@@ -703,7 +703,7 @@ const char *fabber_nlls_kernel_name(const fvb_config *cfg);
  * around its body and the engine keeps everything else (a_K, the first sweep in both forms, pack). With an entry next to
  * a body of the same name in the registry of fabber_vb_register_device_model, fabber_vb_run_spatial_host / _device and
  * fabber_vb_spatial_open accept FVB_MODEL_PLUGIN for that name and parameter count under white noise with one precision
- * (-40 otherwise, as before; -52 without cfg->init_mvn unless the library registered an init entry for the name,
+ * (AR(1) noise and noise patterns: the registry further down; -40 otherwise, as before; -52 without cfg->init_mvn unless the library registered an init entry for the name,
  * fabber_vb_register_device_init_model: the spatial kernels themselves know no library's InitVoxelPosterior). `launch`
  * receives which kernel to start (FVB_SPATIAL_KERNEL_*), need_f, the engine's arguments (fvb::SpatialArgs, sizeof =
  * spatial_args_size), the grid size in 64-lane workgroups and the dynamic LDS bytes as the engine worked them out; it
@@ -736,9 +736,51 @@ int32_t fabber_vb_device_spatial_model_count(void);
 const char *fabber_vb_device_spatial_model_name(int32_t i); /* NULL when i is out of range */
 int32_t fabber_vb_device_spatial_model_params(int32_t i);   /* 0 when i is out of range */
 
-/* Which kernel table fabber_vb_run_spatial_* would take for a configuration: "spatial<exp,2>" / "spatial<NAME,P>" ..., ""
- * where the run would answer -40 or -44 (no kernels for the model / parameter count / noise model; a library body
- * without a spatial entry). Reads n_params, n_phis, noise, ar_cross_terms, need_f, model and device_model. */
+/*
+ * The spatial VB kernels for such a body under AR(1) noise and under a noise pattern (FABBER_DEVICE_SPATIAL_NOISE_MODEL in
+ * include/fabber_device_spatial_noise_model.h): a registry of its own keyed by (name, n_params), 1 <= n_params <= 6,
+ * independent of the one above (an entry needs a body of its name, not a white-noise spatial entry). `families` says which
+ * noise policies the library compiled its set-up kernel and second sweep around: FVB_SPATIAL_NOISE_AR1 = AR(1) noise with
+ * one echo, FVB_SPATIAL_NOISE_PHIS = white noise with 2 precisions and with 3 to 4. Two echoes and 5 to 8 precisions have no
+ * library kernels (-40 from the run, as before). state_rows_*: the rows of the state image the family's kernels were
+ * compiled for (fvb::SpLayout<P>::ROWS plus the policy's own), 0 for a family that is absent; the engine takes an entry
+ * only where they equal its own table's. `launch` is the launcher of the registry above with the noise kind in front (the
+ * engine's number of the policy: 1 = 2 precisions, 2 = 3 to 4 precisions, 3 = AR(1)); the dynamic LDS bytes are the
+ * engine's (the pattern kernels keep one class byte per timepoint there: a launcher passes the count on and never computes
+ * one). It answers -40 with its message for a kind outside its mask.
+ * Registration is refused with -65 (descriptor, name or launcher NULL, name too long, n_params outside 1 ... 6, a mask that
+ * is empty or names a family the engine does not know, a negative row count), -66 (another ABI version), -67 (another
+ * sizeof(fvb::SpatialArgs)) or -68 (duplicate entry); unregistering an entry that does not exist answers -69. The lifetime
+ * rules are those of fabber_vb_register_device_model.
+ */
+#define FVB_SPATIAL_NOISE_AR1 1
+#define FVB_SPATIAL_NOISE_PHIS 2
+typedef int32_t (*fvb_device_spatial_noise_launch_fn)(int32_t kind, int32_t which, int32_t need_f, const void *spatial_args,
+                                                      uint32_t grid, uint32_t lds_bytes, void *stream, char *err, int32_t err_len);
+typedef struct fvb_device_spatial_noise_model
+{
+    const char *name;
+    int32_t abi_version;        /* FVB_ABI_VERSION the library was compiled against */
+    uint32_t spatial_args_size; /* sizeof(fvb::SpatialArgs) */
+    int32_t n_params;
+    int32_t families;           /* FVB_SPATIAL_NOISE_AR1 | FVB_SPATIAL_NOISE_PHIS: not empty */
+    int32_t state_rows_ar1;     /* SpLayout<P>::ROWS + SpAr1<P>::EXTRA_ROWS */
+    int32_t state_rows_phis2;   /* SpLayout<P>::ROWS + SpPattern<P, 2>::EXTRA_ROWS */
+    int32_t state_rows_phis4;   /* SpLayout<P>::ROWS + SpPattern<P, 4>::EXTRA_ROWS */
+    fvb_device_spatial_noise_launch_fn launch;
+} fvb_device_spatial_noise_model;
+int32_t fabber_vb_register_device_spatial_noise_model(const fvb_device_spatial_noise_model *model);
+int32_t fabber_vb_unregister_device_spatial_noise_model(const char *name, int32_t n_params);
+int32_t fabber_vb_device_spatial_noise_model_count(void);
+const char *fabber_vb_device_spatial_noise_model_name(int32_t i); /* NULL when i is out of range */
+int32_t fabber_vb_device_spatial_noise_model_params(int32_t i);   /* 0 when i is out of range */
+/* A copy of the entry for (name, n_params) in *entry - its mask, its row counts, its launcher - and 1; 0 without one. */
+int32_t fabber_vb_find_device_spatial_noise_model(const char *name, int32_t n_params, fvb_device_spatial_noise_model *entry);
+
+/* Which kernel table fabber_vb_run_spatial_* would take for a configuration: "spatial<exp,2>" / "spatial<NAME,P>" /
+ * "spatial<NAME,P,ar1>" ..., "" where the run would answer -40 or -44 (no kernels for the model / parameter count / noise
+ * model; a library body without a spatial entry for the noise model). Reads n_params, n_phis, noise, ar_cross_terms,
+ * need_f, model and device_model. */
 const char *fabber_vb_spatial_kernel_name(const fvb_config *cfg);
 
 /* The engine's work buffers (the re-laid series, the spatial run's state) come from the current device's
