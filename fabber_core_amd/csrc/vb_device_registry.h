@@ -35,8 +35,12 @@ struct DeviceStructSize
 template <class D> struct DeviceRegistryTraits;
 
 // The key of an entry is (name, parameter count); the descriptors of the wave body, of the result-image kernel and of
-// the initial-posterior kernel have no count: 0
+// the initial-posterior kernel have no count, nor have the wave-per-voxel spatial kernels (a runtime value there): 0
 inline int registered_params(const fvb_device_model &)
+{
+    return 0;
+}
+inline int registered_params(const fvb_device_spatial_wave_model &)
 {
     return 0;
 }

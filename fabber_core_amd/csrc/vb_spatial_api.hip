@@ -87,6 +87,33 @@ template <> struct DeviceRegistryTraits<fvb_device_spatial_noise_model>
         return "no " + entry(name, n_params) + " are registered";
     }
 };
+// ... and the two kernels of the wave-per-voxel family compiled around a body (include/fabber_device_spatial_wave_model.h),
+// by name: the parameter count is a runtime value there. vb_spatial_wave.hip has the table and the layout these go with.
+SpatialKernels get_spatial_kernels_wave_model(int P, bool need_f);
+uint32_t spatial_wave_model_lds_probe();
+size_t spatial_wave_layout_size(); // sizeof(WaveLayout)
+template <> struct DeviceRegistryTraits<fvb_device_spatial_wave_model>
+{
+    static constexpr const char *noun = "device spatial wave model", *is = "are";
+    static constexpr int first_code = -35;
+    static std::vector<DeviceStructSize> sizes(const fvb_device_spatial_wave_model &m)
+    {
+        return { { "SpatialArgs", m.spatial_args_size, sizeof(SpatialArgs) }, { "WaveLayout", m.wave_layout_size, spatial_wave_layout_size() },
+            { "LDS doubles at FVB_MAX_PARAMS parameters", m.lds_probe, spatial_wave_model_lds_probe() } };
+    }
+    static const char *bad_params(const fvb_device_spatial_wave_model &)
+    {
+        return nullptr;
+    }
+    static std::string entry(const std::string &name, int)
+    {
+        return "wave-per-voxel spatial kernels of a device model named '" + name + "'";
+    }
+    static std::string absent(const std::string &name, int)
+    {
+        return "no " + entry(name, 0) + " are registered";
+    }
+};
 } // namespace fvb
 namespace
 {
@@ -110,9 +137,11 @@ thread_local std::string g_spatial_kernel_name;
 // A body of a model library: the table of the parameter count with the engine's own kernels wherever the model plays no
 // part - the linear model's table serves, it covers 1 ... 8 parameters - and the three that evaluate the model left to
 // the library's launcher. Under a noise pattern of 2 to 4 precisions and under AR(1) noise with one echo the same with the
-// policy's table and the launcher of the library's entry for these policies (spatial_route_library_noise). Nothing (-40)
-// without an entry for (name, P) that covers the noise model, under the other noise models, or for a name without a
-// wave body (which the argument checks answer with -16 before this is asked).
+// policy's table and the launcher of the library's entry for these policies (spatial_route_library_noise). Without a lane
+// entry for (name, P) under white noise with one precision: the wave-per-voxel family around the body, where the library
+// registered it (spatial_route_library_wave). Nothing (-40) without an entry that covers the parameter count and the noise
+// model, under the other noise models, or for a name without a wave body (which the argument checks answer with -16
+// before this is asked).
 static SpatialRoute spatial_route_library_noise(const fvb_config *cfg, int kind, const std::string &name)
 {
     SpatialRoute route;
@@ -136,6 +165,25 @@ static SpatialRoute spatial_route_library_noise(const fvb_config *cfg, int kind,
     route.kind = kind;
     return route;
 }
+// White noise with one precision and no lane entry for (name, P): the wave-per-voxel family where the library compiled its
+// set-up kernel and second sweep around the body (include/fabber_device_spatial_wave_model.h), any parameter count the
+// family takes. The engine's a_K kernels, first sweep and pack kernel of get_spatial_kernels_wide, the LDS of the layout
+// with the body's parameter vectors; no split first sweep (prep, noise_fast are NULL: the run never asks for
+// FVB_SPATIAL_KERNEL_NOISE_SPLIT).
+static SpatialRoute spatial_route_library_wave(const fvb_config *cfg, const std::string &name)
+{
+    SpatialRoute route;
+    fvb_device_spatial_wave_model entry;
+    if (cfg->n_params < 1 || cfg->n_params > FVB_MAX_PARAMS || !DeviceRegistry<fvb_device_spatial_wave_model>::instance().find(name, 0, &entry))
+        return route;
+    const SpatialKernels k = get_spatial_kernels_wave_model(cfg->n_params, cfg->need_f != 0);
+    if (!k.theta || !k.wave)
+        return route;
+    route.name = "spatial<" + name + ",wave>";
+    route.k = k;
+    route.library = entry.launch;
+    return route;
+}
 static SpatialRoute spatial_route_library(const fvb_config *cfg, int kind)
 {
     SpatialRoute route;
@@ -146,7 +194,7 @@ static SpatialRoute spatial_route_library(const fvb_config *cfg, int kind)
     if (kind != FVB_SPNZ_WHITE)
         return spatial_route_library_noise(cfg, kind, name);
     if (!DeviceRegistry<fvb_device_spatial_model>::instance().find(name, cfg->n_params, &entry))
-        return route;
+        return spatial_route_library_wave(cfg, name);
     SpatialKernels k = get_spatial_kernels_linear(cfg->n_params, cfg->need_f != 0);
     if (!k.setup || k.wave || k.lds_classes || k.state_rows != entry.state_rows) // (state_rows: compiled against another SpLayout)
         return route;
@@ -1004,6 +1052,31 @@ int32_t fabber_vb_device_spatial_noise_model_params(int32_t i)
 int32_t fabber_vb_find_device_spatial_noise_model(const char *name, int32_t n_params, fvb_device_spatial_noise_model *entry)
 {
     return (name && entry && DeviceRegistry<fvb_device_spatial_noise_model>::instance().find(name, n_params, entry)) ? 1 : 0;
+}
+
+int32_t fabber_vb_register_device_spatial_wave_model(const fvb_device_spatial_wave_model *model)
+{
+    return DeviceRegistry<fvb_device_spatial_wave_model>::instance().add(model);
+}
+
+int32_t fabber_vb_unregister_device_spatial_wave_model(const char *name)
+{
+    return DeviceRegistry<fvb_device_spatial_wave_model>::instance().remove(name, 0);
+}
+
+int32_t fabber_vb_device_spatial_wave_model_count(void)
+{
+    return DeviceRegistry<fvb_device_spatial_wave_model>::instance().count();
+}
+
+const char *fabber_vb_device_spatial_wave_model_name(int32_t i)
+{
+    return DeviceRegistry<fvb_device_spatial_wave_model>::instance().name(i);
+}
+
+int32_t fabber_vb_find_device_spatial_wave_model(const char *name, fvb_device_spatial_wave_model *entry)
+{
+    return (name && entry && DeviceRegistry<fvb_device_spatial_wave_model>::instance().find(name, 0, entry)) ? 1 : 0;
 }
 
 // (the selection function of the run: "" where open() would answer -40 or -44)

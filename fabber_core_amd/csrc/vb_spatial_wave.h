@@ -19,6 +19,10 @@
  * SPW_TC timepoints of J are staged in LDS and every lane adds its share of the P (P + 1) / 2 + P + 1 sums over t in
  * order, so T has no limit here. fp64 throughout; sums run in orders of their own (the lane form's rounding is not
  * reproduced bit for bit - the oracle is the yardstick).
+ *
+ * The set-up kernel and the second sweep are templates on where a chunk of the linearisation comes from (SpwHostRows
+ * below: the host's rows): vb_spatial_wave_model.h builds them around the device body of a model library, which they
+ * linearise in the kernel.
  */
 #pragma once
 
@@ -102,10 +106,10 @@ FVB_HD WaveLayout sp_wave_layout(int P)
 // the entries one lane accumulates in spw_moments: P (P + 1) / 2 + P + 1 <= 561 at P = 32, 64 lanes
 constexpr int SPW_MAX_SLOTS = (FVB_MAX_PARAMS * (FVB_MAX_PARAMS + 1) / 2 + FVB_MAX_PARAMS + 1 + 63) / 64;
 
-__device__ __forceinline__ void spw_init_ctx(WaveCtx &cx, int v, size_t V, int P)
+__device__ __forceinline__ void spw_init_ctx(WaveCtx &cx, int v, size_t V, const WaveLayout &L)
 {
     extern __shared__ double spw_lds[];
-    cx.L = sp_wave_layout(P);
+    cx.L = L;
     cx.sh = spw_lds;
     cx.phi = nullptr;
     cx.lane = threadIdx.x;
@@ -230,9 +234,39 @@ __device__ __forceinline__ void spw_stage_chunk(const KernelArgs &ka, WaveCtx &c
     wave_sync();
 }
 
-// The moments about the linearisation `lin` (recentre with HostLinModel): A = J'J, u = J'r, s = r'r over the unmasked
+// Where the set-up kernel and the second sweep take the model's linearisation from, chunk by chunk - what they are
+// templates on (Rows):
+//   Rows(sa, v, next)    voxel v's source; next = false: the linearisation the moments in the state belong to
+//   layout(P)            the LDS layout of the kernels built around the source (sp_wave_layout, or an extension of it)
+//   centre(ka, cx)       once before the chunks of a pass: the linearisation is about the centre in L.ml
+//   chunk(ka, cx, phi_index, t0, n, bad_offset, bad_jac)    spw_stage_chunk's contract for the chunk [t0, t0 + n)
+// SpwHostRows: the rows the host computed (HostLin of vb_spatial_api.hip). vb_spatial_wave_model.h has the source that
+// evaluates a model library's device body.
+struct SpwHostRows
+{
+    const double *lin;
+    __device__ __forceinline__ SpwHostRows(const SpatialArgs &sa, int v, bool next)
+        : lin((next ? sa.lin_next : sa.lin_cur) + (size_t)v * sa.ka.cfg.n_times * (sa.ka.cfg.n_params + 1))
+    {
+    }
+    static __device__ __forceinline__ WaveLayout layout(int P)
+    {
+        return sp_wave_layout(P);
+    }
+    __device__ __forceinline__ void centre(const KernelArgs &, WaveCtx &) const
+    {
+    }
+    __device__ __forceinline__ void chunk(const KernelArgs &ka, WaveCtx &cx, const uint8_t *phi_index, int t0, int n, bool &bad_offset,
+        bool &bad_jac) const
+    {
+        spw_stage_chunk(ka, cx, lin, phi_index, t0, n, bad_offset, bad_jac);
+    }
+};
+
+// The moments about the linearisation of `rows` (recentre with HostLinModel): A = J'J, u = J'r, s = r'r over the unmasked
 // timepoints, each a sum over t in order. The centre (L.ml) is the caller's. Returns the re-centre's status.
-__device__ __forceinline__ int spw_moments(const KernelArgs &ka, WaveCtx &cx, const double *lin)
+template <class Rows>
+__device__ __forceinline__ int spw_moments(const KernelArgs &ka, WaveCtx &cx, const Rows &rows)
 {
     const WaveLayout &L = cx.L;
     const int T = ka.cfg.n_times, P = L.P, Ps = L.Ps, PT = L.PT;
@@ -267,10 +301,11 @@ __device__ __forceinline__ int spw_moments(const KernelArgs &ka, WaveCtx &cx, co
         }
     }
     bool bad_offset = false, bad_jac = false;
+    rows.centre(ka, cx);
     for (int t0 = 0; t0 < T; t0 += SPW_TC)
     {
         const int n = (T - t0 < SPW_TC) ? T - t0 : SPW_TC;
-        spw_stage_chunk(ka, cx, lin, phi_index, t0, n, bad_offset, bad_jac);
+        rows.chunk(ka, cx, phi_index, t0, n, bad_offset, bad_jac);
 #pragma unroll
         for (int k = 0; k < SPW_MAX_SLOTS; k++)
         {
@@ -364,7 +399,8 @@ __device__ __forceinline__ void spw_moment_residual(WaveCtx &cx, double &kk, dou
 
 // k'k with k = y - g(ml) + J (ml - m) summed directly over the unmasked timepoints in order (noisemodel_white.cc:235,252),
 // g and J from the linearisation the moments in the state belong to
-__device__ __forceinline__ double spw_direct_residual(const KernelArgs &ka, WaveCtx &cx, const double *lin)
+template <class Rows>
+__device__ __forceinline__ double spw_direct_residual(const KernelArgs &ka, WaveCtx &cx, const Rows &rows)
 {
     const WaveLayout &L = cx.L;
     const int T = ka.cfg.n_times, P = L.P, Ps = L.Ps;
@@ -374,10 +410,11 @@ __device__ __forceinline__ double spw_direct_residual(const KernelArgs &ka, Wave
     sh[L.pv + i] = sh[L.ml + i] - sh[L.m + i];
     bool bad_offset = false, bad_jac = false; // (the set-up or the previous re-centre has reported these already)
     double kk = 0;
+    rows.centre(ka, cx);
     for (int t0 = 0; t0 < T; t0 += SPW_TC)
     {
         const int n = (T - t0 < SPW_TC) ? T - t0 : SPW_TC;
-        spw_stage_chunk(ka, cx, lin, phi_index, t0, n, bad_offset, bad_jac);
+        rows.chunk(ka, cx, phi_index, t0, n, bad_offset, bad_jac);
         FVB_WAVE_FOR(t, n)
         {
             double Jd = 0;
@@ -407,16 +444,17 @@ __device__ __forceinline__ void spw_set_residual(const KernelArgs &ka, WaveCtx &
 }
 
 // ---- setup: Vb::SetupPerVoxelDists (inference_vb.cc:207-247), one workgroup per voxel ------------------------------
-__global__ __launch_bounds__(64) void vb_spatial_wave_setup_kernel(const SpatialArgs sa)
+template <class Rows>
+__device__ __forceinline__ void spw_setup(const SpatialArgs &sa)
 {
     const KernelArgs &ka = sa.ka;
     const int v = blockIdx.x;
     const size_t V = (size_t)ka.cfg.n_voxels;
     if (v >= ka.cfg.n_voxels)
         return;
-    const int P = ka.cfg.n_params, T = ka.cfg.n_times;
+    const int P = ka.cfg.n_params;
     WaveCtx cx;
-    spw_init_ctx(cx, v, V, P);
+    spw_init_ctx(cx, v, V, Rows::layout(P));
     const WaveLayout &L = cx.L;
     const SpWideLayout S = sp_wide_layout(P);
     double *sh = cx.sh;
@@ -464,11 +502,20 @@ __global__ __launch_bounds__(64) void vb_spatial_wave_setup_kernel(const Spatial
     }
     wave_sync();
     cx.logdetLam = 0;
-    const int status = spw_moments(ka, cx, sa.lin_next + (size_t)v * T * (P + 1));
+    const int status = spw_moments(ka, cx, Rows(sa, v, true));
     if (cx.lane == 0)
         sa.status[v] = status ? (status | 0x100) : 0;
     spw_store_theta(sa, cx);
     spw_store_noise(sa, cx);
+}
+
+// The kernels that are no templates are the engine's alone (vb_spatial_wave.hip defines FVB_SPATIAL_WAVE_ENGINE): a model
+// library includes this header in several of its sources for the templates (vb_spatial_wave_model.h) and must not
+// define them again.
+#if defined(FVB_SPATIAL_WAVE_ENGINE)
+__global__ __launch_bounds__(64) void vb_spatial_wave_setup_kernel(const SpatialArgs sa)
+{
+    spw_setup<SpwHostRows>(sa);
 }
 
 // ---- CalculateaK (priors.cc:221-344), runtime P: the lane form's segments, sums and order -------------------------
@@ -580,6 +627,7 @@ __global__ void vb_spatial_wide_ak_final_kernel(const SpatialArgs sa)
         aK = aKMax;
     sa.aK[k] = aK;
 }
+#endif // FVB_SPATIAL_WAVE_ENGINE
 
 // SpatialPrior::ApplyToMVN (priors.cc:362-482) and the other priors of voxel cx.v, one parameter per lane, as
 // vb_spatial_theta_kernel codes them (second_order_rec, the status tests on the END points of second-neighbour
@@ -710,7 +758,7 @@ __global__ __launch_bounds__(64) void vb_spatial_wave_theta_kernel(const Spatial
     if (ignored && v != sa.owned_end - 1)
         return;
     WaveCtx cx;
-    spw_init_ctx(cx, v, (size_t)ka.cfg.n_voxels, ka.cfg.n_params);
+    spw_init_ctx(cx, v, (size_t)ka.cfg.n_voxels, sp_wave_layout(ka.cfg.n_params));
     spw_load(sa, cx);
     const double Fprior = spw_apply_priors(sa, cx, it);
     if (v == sa.owned_end - 1 && cx.lane == 0)
@@ -750,8 +798,8 @@ __global__ __launch_bounds__(64) void vb_spatial_wave_theta_kernel(const Spatial
 }
 
 // ---- second sweep: UpdateNoise, ReCentre, F (inference_vb.cc:674-722), one workgroup per owned voxel ----------------
-template <bool NEEDF>
-__global__ __launch_bounds__(64) void vb_spatial_wave_noise_kernel(const SpatialArgs sa)
+template <class Rows, bool NEEDF>
+__device__ __forceinline__ void spw_noise(const SpatialArgs &sa)
 {
     const KernelArgs &ka = sa.ka;
     const int v = sa.owned_begin + blockIdx.x;
@@ -759,14 +807,14 @@ __global__ __launch_bounds__(64) void vb_spatial_wave_noise_kernel(const Spatial
         return;
     if (sa.status[v] != 0)
         return;
-    const int P = ka.cfg.n_params, T = ka.cfg.n_times;
+    const int P = ka.cfg.n_params;
     WaveCtx cx;
-    spw_init_ctx(cx, v, (size_t)ka.cfg.n_voxels, P);
+    spw_init_ctx(cx, v, (size_t)ka.cfg.n_voxels, Rows::layout(P));
     spw_load(sa, cx);
     const WaveLayout &L = cx.L;
     double *sh = cx.sh;
     // the residual about the centre the moments belong to ...
-    double kk = spw_direct_residual(ka, cx, sa.lin_cur + (size_t)v * T * (P + 1));
+    double kk = spw_direct_residual(ka, cx, Rows(sa, v, false));
     double trSA = spw_trace_SA(cx);
     spw_set_residual(ka, cx, kk, trSA);
     wave_update_noise(ka, cx);
@@ -777,7 +825,7 @@ __global__ __launch_bounds__(64) void vb_spatial_wave_noise_kernel(const Spatial
         FVB_WAVE_FOR(i, P)
         sh[L.ml + i] = sh[L.m + i];
         wave_sync();
-        status = spw_moments(ka, cx, sa.lin_next + (size_t)v * T * (P + 1));
+        status = spw_moments(ka, cx, Rows(sa, v, true));
         kk = sh[L.s]; // the centre is the mean now: k = y - g
         trSA = spw_trace_SA(cx);
     }
@@ -801,8 +849,14 @@ __global__ __launch_bounds__(64) void vb_spatial_wave_noise_kernel(const Spatial
         sa.status[v] = status;
     spw_store_noise(sa, cx);
 }
+template <bool NEEDF>
+__global__ __launch_bounds__(64) void vb_spatial_wave_noise_kernel(const SpatialArgs sa)
+{
+    spw_noise<SpwHostRows, NEEDF>(sa);
+}
 
 // ---- result image (inference_vb.cc:757-762), lane per voxel ---------------------------------------------------------
+#if defined(FVB_SPATIAL_WAVE_ENGINE)
 __global__ __launch_bounds__(256) void vb_spatial_wide_pack_kernel(const SpatialArgs sa)
 {
     const KernelArgs &ka = sa.ka;
@@ -832,6 +886,7 @@ __global__ __launch_bounds__(256) void vb_spatial_wide_pack_kernel(const Spatial
     if (ka.out.free_energy && !ka.cfg.need_f)
         ka.out.free_energy[v] = 1234.5678;
 }
+#endif // FVB_SPATIAL_WAVE_ENGINE
 
 #endif // __HIPCC__
 

@@ -1,5 +1,6 @@
 // Spatial-VB kernels of the wave-per-voxel family (vb_spatial_wave.h): host-evaluated models, runtime parameter count
-#include "vb_spatial_wave.h"
+#define FVB_SPATIAL_WAVE_ENGINE 1 // (the family's kernels that are no templates are defined here, once)
+#include "vb_spatial_wave_model.h"
 
 namespace fvb
 {
@@ -22,5 +23,29 @@ SpatialKernels get_spatial_kernels_wide(int P, bool need_f)
     k.wave = 1;
     k.wave_lds = sp_wave_layout(P).bytes;
     return k;
+}
+
+// The family around the device body of a model library (vb_spatial_wave_model.h,
+// include/fabber_device_spatial_wave_model.h): the table above with the two kernels that read the linearisation left to
+// the library's launcher and the LDS of the layout those kernels place their arrays in (the engine's first sweep uses
+// the front of it: sp_wave_layout's offsets are that layout's).
+SpatialKernels get_spatial_kernels_wave_model(int P, bool need_f)
+{
+    SpatialKernels k = get_spatial_kernels_wide(P, need_f);
+    if (!k.theta)
+        return k;
+    k.setup = k.noise = nullptr; // the library's
+    k.name = nullptr;
+    k.wave_lds = sp_wave_model_layout(P).bytes;
+    return k;
+}
+// what a library's entry must report as its lds_probe and as its wave_layout_size
+uint32_t spatial_wave_model_lds_probe()
+{
+    return (uint32_t)sp_wave_model_layout(FVB_MAX_PARAMS).n_doubles;
+}
+size_t spatial_wave_layout_size()
+{
+    return sizeof(WaveLayout);
 }
 } // namespace fvb

@@ -24,6 +24,7 @@ _DEVICE_ENTRIES = (("device_model", vbabi.FvbDeviceModel, False),
                    ("device_nlls_model", vbabi.FvbDeviceNllsModel, True),
                    ("device_spatial_model", vbabi.FvbDeviceSpatialModel, True),
                    ("device_spatial_noise_model", vbabi.FvbDeviceSpatialNoiseModel, True),
+                   ("device_spatial_wave_model", vbabi.FvbDeviceSpatialWaveModel, False),
                    ("device_results_model", vbabi.FvbDeviceResultsModel, False),
                    ("device_init_model", vbabi.FvbDeviceInitModel, False))
 
@@ -101,6 +102,8 @@ def lib():
         L.fabber_vb_find_device_lane_noise_model.argtypes = [C.c_char_p, C.c_int32, C.POINTER(vbabi.FvbDeviceLaneNoiseModel)]
         L.fabber_vb_find_device_spatial_noise_model.restype = C.c_int32
         L.fabber_vb_find_device_spatial_noise_model.argtypes = [C.c_char_p, C.c_int32, C.POINTER(vbabi.FvbDeviceSpatialNoiseModel)]
+        L.fabber_vb_find_device_spatial_wave_model.restype = C.c_int32
+        L.fabber_vb_find_device_spatial_wave_model.argtypes = [C.c_char_p, C.POINTER(vbabi.FvbDeviceSpatialWaveModel)]
         L.fabber_nlls_kernel_name.restype = C.c_char_p
         L.fabber_nlls_kernel_name.argtypes = [cfgp]
         L.fabber_vb_spatial_kernel_name.restype = C.c_char_p
@@ -251,6 +254,26 @@ def find_device_spatial_noise_model(name, n_params):
     """a copy of the entry for (name, n_params) - families, rows of the state images, launcher - or None"""
     entry = vbabi.FvbDeviceSpatialNoiseModel()
     return entry if lib().fabber_vb_find_device_spatial_noise_model(name.encode(), n_params, C.byref(entry)) else None
+
+
+def device_spatial_wave_models():
+    """Names of the wave-per-voxel spatial-VB entries registered with the engine (include/fabber_device_spatial_wave_model.h):
+    any parameter count up to FVB_MAX_PARAMS."""
+    return _listed("device_spatial_wave_model", False)
+
+
+def register_device_spatial_wave_model(descriptor):
+    _register("device_spatial_wave_model", descriptor)
+
+
+def unregister_device_spatial_wave_model(name):
+    _unregister("device_spatial_wave_model", name)
+
+
+def find_device_spatial_wave_model(name):
+    """a copy of the entry of `name` - the sizes and the LDS probe it reported, launcher - or None"""
+    entry = vbabi.FvbDeviceSpatialWaveModel()
+    return entry if lib().fabber_vb_find_device_spatial_wave_model(name.encode(), C.byref(entry)) else None
 
 
 def device_results_models():

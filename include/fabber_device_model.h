@@ -47,14 +47,15 @@
  * whole wavefront. The host side asks for them with spec.uses_suppdata = true (DeviceModelSpec); the engine then hands
  * the body the run's supplementary data, all rows, on every route of this family of headers, spatial VB included: the
  * kernels of fabber_device_spatial_model.h and fabber_device_spatial_noise_model.h set them for the voxel their lane
- * works on. Without the spatial line for the run's parameter count and noise model, method=spatialvb runs such a model
+ * works on, those of fabber_device_spatial_wave_model.h for the voxel of their wavefront. Without the spatial line for the run's parameter count and noise model, method=spatialvb runs such a model
  * on the host route (the log says so).
  *
  * The expression must be
  * the one the model's host EvaluateModel computes - the host code still provides the initial posterior unless the
  * library also uses the macro of fabber_device_init_model.h, the extra outputs of save-model-extras, model fit and
  * residuals unless the library also uses the macro of fabber_device_results_model.h, and the whole fit wherever the device body is not used (the host-model option, spatial
- * VB unless the library also uses the macros of fabber_device_spatial_model.h / fabber_device_spatial_noise_model.h, and method=nlls unless it uses those of
+ * VB unless the library also uses the macros of fabber_device_spatial_model.h / fabber_device_spatial_noise_model.h /
+ * fabber_device_spatial_wave_model.h, and method=nlls unless it uses those of
  * fabber_device_nlls_model.h).
  *
  * The macro, at namespace scope, once per model:
@@ -77,7 +78,9 @@
  * parameter count, next to the line above. The NLLS minimisers of method=nlls (one wavefront or one lane per voxel, the
  * whole minimisation in one launch) are compiled around it by fabber_device_nlls_model.h in the same way, the two
  * kernels of spatial VB that evaluate the model by fabber_device_spatial_model.h (white noise with one precision) and
- * fabber_device_spatial_noise_model.h (AR(1) noise, noise patterns), and the result-image kernel (model fit
+ * fabber_device_spatial_noise_model.h (AR(1) noise, noise patterns) for 1 to 6 parameters and by
+ * fabber_device_spatial_wave_model.h for any count up to FVB_MAX_PARAMS (one wavefront per voxel, white noise with one
+ * precision), and the result-image kernel (model fit
  * and residuals) by fabber_device_results_model.h, and the initial-posterior kernel - around one more member of the body,
  * init_posterior - by fabber_device_init_model.h.
  */

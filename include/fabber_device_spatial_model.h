@@ -22,9 +22,11 @@
  * The engine takes these kernels for a configuration when an entry for (name, n_params) is registered and the noise is
  * white with one precision; the kernel table's name is spatial<NAME,P>. Noise patterns of 2 to 4 precisions and AR(1)
  * noise with one echo are a macro line of fabber_device_spatial_noise_model.h (FABBER_DEVICE_SPATIAL_NOISE_MODEL); without
- * it they, and in any case other parameter counts, two echoes, 5 to 8 precisions and a volume cut into z-slabs over
- * several devices, keep the host route (-40 from the engine, after which method=spatialvb evaluates the model's host code
- * as before). A body that reads the voxel's supplementary data (fvb::supp_at, spec.uses_suppdata) receives the rows of
+ * it they, and in any case two echoes, 5 to 8 precisions and a volume cut into z-slabs over several devices, keep the host
+ * route (-40 from the engine, after which method=spatialvb evaluates the model's host code as before). Other parameter
+ * counts keep it too unless the library has the line of fabber_device_spatial_wave_model.h (FABBER_DEVICE_SPATIAL_WAVE_MODEL:
+ * one wavefront per voxel, any count up to FVB_MAX_PARAMS under white noise with one precision; an entry of THIS header
+ * for the run's count comes first). A body that reads the voxel's supplementary data (fvb::supp_at, spec.uses_suppdata) receives the rows of
  * the voxel its lane works on, as in the kernels of voxelwise VB. The initial posterior is an image (init_mvn): these
  * kernels know no library's InitVoxelPosterior. It comes from the model's host code, or - where the library also uses the
  * macro of fabber_device_init_model.h - from the kernel the engine launches ahead of the set-up kernel. The body is evaluated pointwise, as in the lane kernels.

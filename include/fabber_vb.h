@@ -627,6 +627,10 @@ void fabber_vb_test_unlink_slab_pair(int32_t pair);
  * Parameter counts: up to 8 with one voxel per lane, under every noise model spatial VB takes (noise patterns and
  * AR(1) noise up to 6); 9 to FVB_MAX_PARAMS (32) with one wavefront per voxel, white noise with one noise precision
  * only (-40 otherwise). More than FVB_MAX_PARAMS: refused (-4).
+ * A model library whose device body has spatial entries does not come here: 1 to 6 parameters run the lane kernels of
+ * include/fabber_device_spatial_model.h / fabber_device_spatial_noise_model.h, any count up to FVB_MAX_PARAMS under white
+ * noise with one precision the wave-per-voxel kernels of include/fabber_device_spatial_wave_model.h, which linearise the
+ * body on the device (fabber_vb_run_spatial_host).
  */
 int32_t fabber_vb_run_spatial_hostmodel_host(const fvb_config *cfg, const fvb_spatial *sp, const void *data, const fvb_outputs *out,
     int32_t device, fvb_linearise_fn linearise, void *user, void (*progress_cb)(int, int));
@@ -777,10 +781,45 @@ int32_t fabber_vb_device_spatial_noise_model_params(int32_t i);   /* 0 when i is
 /* A copy of the entry for (name, n_params) in *entry - its mask, its row counts, its launcher - and 1; 0 without one. */
 int32_t fabber_vb_find_device_spatial_noise_model(const char *name, int32_t n_params, fvb_device_spatial_noise_model *entry);
 
+/*
+ * The spatial VB kernels for such a body with ONE WAVEFRONT per voxel (FABBER_DEVICE_SPATIAL_WAVE_MODEL in
+ * include/fabber_device_spatial_wave_model.h): a registry of its own keyed by the name alone - the parameter count is a
+ * runtime value of this family, 1 to FVB_MAX_PARAMS. The library compiles the set-up kernel and the second sweep of the
+ * wave-per-voxel spatial family (csrc/vb_spatial_wave.h) around its body, which they linearise by the reference's central
+ * differences; the a_K kernels, the first sweep and the result image stay the engine's. With an entry next to a body of the
+ * same name in the registry of fabber_vb_register_device_model, fabber_vb_run_spatial_host / _device and
+ * fabber_vb_spatial_open take these kernels for FVB_MODEL_PLUGIN under white noise with one precision wherever the registry
+ * of fabber_vb_register_device_spatial_model has no entry for (name, n_params): the kernel table's name is
+ * spatial<NAME,wave>. Every other noise model keeps -40, as before; the initial posterior is found as for the entries of
+ * that registry (-52). `launch` is the launcher type of that registry: FVB_SPATIAL_KERNEL_SETUP and FVB_SPATIAL_KERNEL_NOISE
+ * with one 64-lane workgroup per voxel and the engine's dynamic LDS bytes; the family has no split form and
+ * FVB_SPATIAL_KERNEL_NOISE_SPLIT is never asked of it. lds_probe is the number of doubles of the family's LDS layout at
+ * FVB_MAX_PARAMS parameters as the library's headers lay it out (fvb::sp_wave_model_layout): the engine works the LDS bytes
+ * out, the library's kernels place their arrays in them, and a library whose layout is another is refused.
+ * Registration is refused with -35 (descriptor, name or launcher NULL, name too long), -36 (another ABI version), -37
+ * (another sizeof(fvb::SpatialArgs) or sizeof(fvb::WaveLayout), another LDS layout) or -38 (duplicate name); unregistering
+ * a name that is not registered answers -39. The lifetime rules are those of fabber_vb_register_device_model.
+ */
+typedef struct fvb_device_spatial_wave_model
+{
+    const char *name;
+    int32_t abi_version;        /* FVB_ABI_VERSION the library was compiled against */
+    uint32_t spatial_args_size; /* sizeof(fvb::SpatialArgs) */
+    uint32_t wave_layout_size;  /* sizeof(fvb::WaveLayout) */
+    uint32_t lds_probe;         /* fvb::sp_wave_model_layout(FVB_MAX_PARAMS).n_doubles */
+    fvb_device_spatial_launch_fn launch;
+} fvb_device_spatial_wave_model;
+int32_t fabber_vb_register_device_spatial_wave_model(const fvb_device_spatial_wave_model *model);
+int32_t fabber_vb_unregister_device_spatial_wave_model(const char *name);
+int32_t fabber_vb_device_spatial_wave_model_count(void);
+const char *fabber_vb_device_spatial_wave_model_name(int32_t i); /* NULL when i is out of range */
+/* A copy of the entry of `name` in *entry and 1; 0 without one. */
+int32_t fabber_vb_find_device_spatial_wave_model(const char *name, fvb_device_spatial_wave_model *entry);
+
 /* Which kernel table fabber_vb_run_spatial_* would take for a configuration: "spatial<exp,2>" / "spatial<NAME,P>" /
- * "spatial<NAME,P,ar1>" ..., "" where the run would answer -40 or -44 (no kernels for the model / parameter count / noise
- * model; a library body without a spatial entry for the noise model). Reads n_params, n_phis, noise, ar_cross_terms,
- * need_f, model and device_model. */
+ * "spatial<NAME,P,ar1>" / "spatial<NAME,wave>" ..., "" where the run would answer -40 or -44 (no kernels for the model /
+ * parameter count / noise model; a library body without a spatial entry for the noise model). Reads n_params, n_phis,
+ * noise, ar_cross_terms, need_f, model and device_model. */
 const char *fabber_vb_spatial_kernel_name(const fvb_config *cfg);
 
 /* The engine's work buffers (the re-laid series, the spatial run's state) come from the current device's

@@ -1,0 +1,10 @@
+"""Builds the test model library whose device bodies bring the wave-per-voxel spatial VB kernels
+(tests/plugins/fwdmodel_spatial_wave_models.hip: multiexp_spw, linear_spw, suppconv_spw, multiexp_both) for the tests and
+the measuring tool of those kernels, with device_model_lib's build of a library from its parts."""
+import device_model_lib
+
+LIBRARY = "libfabber_models_spatial_wave.so"
+
+
+def build_spatial_wave_library():
+    return device_model_lib.build("fwdmodel_spatial_wave_models.hip", (1, 2, 3, 4, 5, 6), LIBRARY)

@@ -1,0 +1,165 @@
+"""method=spatialvb for a model library's body with more parameters than the lane kernels take (the wave-per-voxel spatial
+kernels of include/fabber_device_spatial_wave_model.h) against the host route of the same library, same build, same
+process: a 64^3 volume, 100 timepoints, 10 iterations, for
+
+    multiexp_spw  num-exps=5 (10 parameters)   sum of exponentials, well-separated rates
+    linear_spw    32 cosine regressors         the design in the body's constants block
+
+(tests/plugins/fwdmodel_spatial_wave_models.hip), a spatial prior M on the first parameter.
+
+Whole call: fabber.run from host arrays to result images - the library's device route (kernels spatial<NAME,wave>) and its
+host route (option host-model: every iteration downloads the means, evaluates the model 2 P + 1 times per voxel on host
+threads and uploads the linearisation; the behaviour before these kernels existed) - with 10 and with 2 iterations each. The
+per-iteration figure is the difference / 8, so the set-up (geometry, initial posterior, first linearisation) cancels.
+
+The sweeps of the device route one by one: fabber_vb_spatial_open on a series, an initial posterior and a result image that
+stay on the device, then per iteration the a_K update, the first sweep (one launch per level) and the second sweep, each
+timed with the stream drained after it (time.perf_counter around the call and torch.cuda.synchronize: host timers, launch
+overhead included). The host family's second sweep cannot be started alone - it sits inside the engine's call between the
+upload of the linearisation and the next download - so for the host route the tool gives the whole iteration only.
+
+    python tools/measure/device_spatial_wave_rate.py [--models multiexp_spw,linear_spw] [--size 64] [--json PATH]
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import torch
+
+import device_spatial_wave_lib
+from fabber_core_amd import fabber, hiplib, vbabi
+from fabber_core_amd.device import DeviceProblem
+from fabber_core_amd.spatial_mgpu import _Run
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--models", default="multiexp_spw,linear_spw")
+ap.add_argument("--size", type=int, default=64)
+ap.add_argument("--times", type=int, default=100)
+ap.add_argument("--json", default=None)
+ap.add_argument("--skip-host-route", action="store_true")
+args = ap.parse_args()
+
+library = device_spatial_wave_lib.build_spatial_wave_library()
+hiplib.load_model_library(library)
+SHAPE, T, ITERS, SHORT = (args.size,) * 3, args.times, 10, 2
+coords = vbabi.grid_coords(SHAPE)
+V = coords.shape[1]
+sp = vbabi.SpatialHolder(coords)
+rng = np.random.default_rng(0)
+scale = 1.0 + 0.2 * np.sin(coords[0] / 5.0) * np.cos(coords[1] / 7.0) + 0.05 * np.sin(coords[2] / 3.0)
+results = []
+tmp = tempfile.mkdtemp(prefix="spw_rate_")
+
+
+def multiexp():
+    num, dt = 5, 0.006
+    rates, amps = np.array([0.5, 3.0, 12.0, 40.0, 150.0]), np.array([1.0, 0.8, 0.6, 0.4, 0.3])
+    t = np.arange(T) * dt
+    y = (sum(amps[i] * scale[None, :] * np.exp(-rates[i] * t)[:, None] for i in range(num)) + rng.normal(0, 0.02, (T, V))).astype(np.float32)
+    init = hiplib.initial_mvn(vbabi.build_config(vbabi.MODEL_EXP, V, T, num_exps=num, dt=dt), y)
+    nCov = (2 * num + 1) * (2 * num + 2) // 2
+    for i in range(num):
+        init[nCov + 2 * i], init[nCov + 2 * i + 1] = np.log(amps[i]), np.log(rates[i])
+    holder = vbabi.build_config(vbabi.MODEL_PLUGIN, V, T, device_model="multiexp_spw", num_exps=num, dt=dt, init_mvn=init,
+                                max_iterations=ITERS, param_overrides={"amp1": dict(type="M")},
+                                params=vbabi.model_parameter_defaults(vbabi.MODEL_EXP, num_exps=num))
+    return y, holder, {"model": "multiexp_spw", "num-exps": num, "dt": dt, "param-spatial-priors": "M" + "N" * (2 * num - 1)}, "amp1"
+
+
+def linear():
+    P = 32
+    X = np.cos(np.pi * np.arange(P)[None, :] * (np.arange(T)[:, None] + 0.5) / T)
+    theta = np.stack([scale / (k + 1) for k in range(P)])
+    y = (X @ theta + rng.normal(0, 0.1, (T, V))).astype(np.float32)
+    params = vbabi.model_parameter_defaults(vbabi.MODEL_LINEAR, n_basis=P)
+    ov = {"Parameter_1": dict(type="M")}
+    init = hiplib.initial_mvn(vbabi.build_config(vbabi.MODEL_LINEAR, V, T, design=X, param_overrides=ov), y)
+    n = P + 1
+    for k in range(P):
+        init[n * (n + 1) // 2 + k] = 1.0 / (k + 1)
+    holder = vbabi.build_config(vbabi.MODEL_PLUGIN, V, T, device_model="linear_spw", constants=X, init_mvn=init, max_iterations=ITERS,
+                                param_overrides=ov, params=params)
+    basis = os.path.join(tmp, "design.mat")
+    np.savetxt(basis, X)
+    return y, holder, {"model": "linear_spw", "basis": basis, "param-spatial-priors": "M" + "N" * (P - 1)}, "Parameter_1"
+
+
+def sweeps_one_by_one(name, holder, y):
+    """the device route's a_K update, first sweep and second sweep per iteration, the stream drained after each"""
+    assert hiplib.spatial_kernel_name(holder) == "spatial<%s,wave>" % name
+    prob = DeviceProblem(holder, y, "cuda:0")
+    prob.run_spatial(sp)  # warm-up: code objects, memory pool
+    assert np.count_nonzero(prob.results()["status"]) < max(1, V // 1000)
+    ms = dict(ak=[], first=[], second=[])
+    t_open = time.perf_counter()
+    run = _Run(prob, sp, torch.cuda.current_stream(prob.device))
+    torch.cuda.synchronize()
+    ms_open = (time.perf_counter() - t_open) * 1e3
+    try:
+        for it in range(ITERS):
+            for what, step in (("ak", None), ("first", lambda: run.sweep_levels(it, -2 ** 62, 2 ** 62)), ("second", lambda: run.sweep_noise(it))):
+                t0 = time.perf_counter()
+                if step is None:
+                    if it > 0:
+                        run.set_ak_sums(run.ak_sums())
+                else:
+                    step()
+                torch.cuda.synchronize()
+                ms[what].append((time.perf_counter() - t0) * 1e3)
+    finally:
+        run.close()
+    out = dict(what="sweeps", route="spatial<%s,wave>" % name, voxels=V, timepoints=T, parameters=holder.cfg.n_params, ms_open_with_set_up=ms_open,
+               **{"ms_%s_median" % k: float(np.median(v[1:])) for k, v in ms.items()}, **{"ms_%s_all" % k: v for k, v in ms.items()})
+    results.append(out)
+    print("sweeps  %-28s %7d voxels T=%d P=%d: open + set-up %.1f ms; per iteration (median of iterations 2..%d) a_K %.2f ms, first sweep %.2f ms, "
+          "second sweep %.2f ms" % (out["route"], V, T, holder.cfg.n_params, ms_open, ITERS, out["ms_ak_median"], out["ms_first_median"],
+                                    out["ms_second_median"]), flush=True)
+    del prob
+
+
+def whole_calls(name, y, model_opts, first):
+    data = np.zeros(SHAPE + (T,), dtype=np.float32)
+    data[coords[0], coords[1], coords[2]] = y.T
+    secs = {}
+    routes = [("device route", {}, "kernels spatial<%s,wave>" % name)]
+    if not args.skip_host_route:
+        routes.append(("host route", {"host-model": True}, "the model is evaluated on the host"))
+    for route, extra, expect in routes:
+        # (the device route's first call warms it up - code objects, memory pool - and is repeated; the host route's calls are
+        # long against that)
+        for iters in ((SHORT, SHORT, ITERS) if not extra else (SHORT, ITERS)):
+            opts = dict({"noise": "white", "method": "spatialvb", "max-iterations": iters, "save-mean": True, "allow-bad-voxels": True},
+                        **model_opts, **extra)
+            t0 = time.perf_counter()
+            res = fabber.run(data, opts, model_libs=[library])
+            secs[route, iters] = time.perf_counter() - t0
+            assert expect in res["log"], (route, res["log"][-2000:])
+            print("call    %-28s %-12s %2d iterations %8.3f s   mean %s %.5f" % (name, route, iters, secs[route, iters], first,
+                                                                                float(np.nanmean(res["mean_" + first]))), flush=True)
+        per_it = (secs[route, ITERS] - secs[route, SHORT]) / (ITERS - SHORT)
+        results.append(dict(what="fabber.run", model=name, route=route, voxels=V, timepoints=T, seconds_run_of_10=secs[route, ITERS],
+                            seconds_run_of_2=secs[route, SHORT], seconds_per_iteration=per_it))
+        print("call    %-28s %-12s %.3f s per iteration (run of %d minus run of %d, / %d)" % (name, route, per_it, ITERS, SHORT, ITERS - SHORT), flush=True)
+    if not args.skip_host_route:
+        ratio = dict(what="ratios", model=name, whole_call_host_over_device=secs["host route", ITERS] / secs["device route", ITERS],
+                     per_iteration_host_over_device=((secs["host route", ITERS] - secs["host route", SHORT])
+                                                     / max(1e-9, secs["device route", ITERS] - secs["device route", SHORT])))
+        results.append(ratio)
+        print("ratios  %-28s host route / device route: whole call of %d iterations %.2f, per iteration %.2f"
+              % (name, ITERS, ratio["whole_call_host_over_device"], ratio["per_iteration_host_over_device"]), flush=True)
+
+
+for name in args.models.split(","):
+    y, holder, model_opts, first = {"multiexp_spw": multiexp, "linear_spw": linear}[name]()
+    sweeps_one_by_one(name, holder, y)
+    whole_calls(name, y, model_opts, first)
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(results, fh, indent=1)
