@@ -44,6 +44,10 @@ inline int registered_params(const fvb_device_spatial_wave_model &)
 {
     return 0;
 }
+inline int registered_params(const fvb_device_spatial_wave_noise_model &)
+{
+    return 0;
+}
 inline int registered_params(const fvb_device_init_model &)
 {
     return 0;

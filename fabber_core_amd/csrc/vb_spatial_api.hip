@@ -114,6 +114,35 @@ template <> struct DeviceRegistryTraits<fvb_device_spatial_wave_model>
         return "no " + entry(name, 0) + " are registered";
     }
 };
+// ... and the same two kernels in their form for 2 to FVB_MAX_PHIS noise precisions
+// (include/fabber_device_spatial_wave_noise_model.h), by name: a registry of its own, an entry says which families its
+// library compiled.
+SpatialKernels get_spatial_kernels_wave_noise_model(int P, int N, bool need_f);
+uint32_t spatial_wave_noise_model_lds_probe();
+hipMemPool_t api_pool(); // (vb_api.hip: the engine's stream-ordered pool of the current device, or NULL)
+template <> struct DeviceRegistryTraits<fvb_device_spatial_wave_noise_model>
+{
+    static constexpr const char *noun = "device spatial wave noise model", *is = "are";
+    static constexpr int first_code = -24;
+    static std::vector<DeviceStructSize> sizes(const fvb_device_spatial_wave_noise_model &m)
+    {
+        return { { "SpatialArgs", m.spatial_args_size, sizeof(SpatialArgs) }, { "WaveLayout", m.wave_layout_size, spatial_wave_layout_size() },
+            { "LDS doubles at FVB_MAX_PARAMS parameters and FVB_MAX_PHIS precisions", m.lds_probe, spatial_wave_noise_model_lds_probe() } };
+    }
+    static const char *bad_params(const fvb_device_spatial_wave_noise_model &m)
+    {
+        return (m.families == 0 || (m.families & ~FVB_SPATIAL_WAVE_NOISE_PHIS) != 0)
+            ? "the families mask does not name FVB_SPATIAL_WAVE_NOISE_PHIS, or names a family this engine does not know" : nullptr;
+    }
+    static std::string entry(const std::string &name, int)
+    {
+        return "wave-per-voxel noise-pattern spatial kernels of a device model named '" + name + "'";
+    }
+    static std::string absent(const std::string &name, int)
+    {
+        return "no " + entry(name, 0) + " are registered";
+    }
+};
 } // namespace fvb
 namespace
 {
@@ -139,7 +168,8 @@ thread_local std::string g_spatial_kernel_name;
 // the library's launcher. Under a noise pattern of 2 to 4 precisions and under AR(1) noise with one echo the same with the
 // policy's table and the launcher of the library's entry for these policies (spatial_route_library_noise). Without a lane
 // entry for (name, P) under white noise with one precision: the wave-per-voxel family around the body, where the library
-// registered it (spatial_route_library_wave). Nothing (-40) without an entry that covers the parameter count and the noise
+// registered it (spatial_route_library_wave); without a lane entry that covers (name, P) under a noise pattern of 2 to 8
+// precisions: the same family in its form for several precisions (spatial_route_library_wave_noise). Nothing (-40) without an entry that covers the parameter count and the noise
 // model, under the other noise models, or for a name without a wave body (which the argument checks answer with -16
 // before this is asked).
 static SpatialRoute spatial_route_library_noise(const fvb_config *cfg, int kind, const std::string &name)
@@ -184,6 +214,25 @@ static SpatialRoute spatial_route_library_wave(const fvb_config *cfg, const std:
     route.library = entry.launch;
     return route;
 }
+// A noise pattern and no lane entry for (name, P) that covers it: the wave-per-voxel family in its form for N = n_phis
+// classes where the library compiled it (include/fabber_device_spatial_wave_noise_model.h). The engine's a_K kernels and
+// pack kernel, its first sweep for N classes, the state image with the class rows, the LDS of the layout for (P, N).
+static SpatialRoute spatial_route_library_wave_noise(const fvb_config *cfg, int kind, const std::string &name)
+{
+    SpatialRoute route;
+    fvb_device_spatial_wave_noise_model entry;
+    if ((kind != FVB_SPNZ_PATTERN2 && kind != FVB_SPNZ_PATTERN4 && kind != FVB_SPNZ_PATTERN8) || cfg->n_params < 1
+        || cfg->n_params > FVB_MAX_PARAMS || !DeviceRegistry<fvb_device_spatial_wave_noise_model>::instance().find(name, 0, &entry)
+        || (entry.families & FVB_SPATIAL_WAVE_NOISE_PHIS) == 0)
+        return route;
+    const SpatialKernels k = get_spatial_kernels_wave_noise_model(cfg->n_params, cfg->n_phis, cfg->need_f != 0);
+    if (!k.theta || !k.wave)
+        return route;
+    route.name = "spatial<" + name + ",wave,phis" + std::to_string(cfg->n_phis) + ">";
+    route.k = k;
+    route.library = entry.launch;
+    return route;
+}
 static SpatialRoute spatial_route_library(const fvb_config *cfg, int kind)
 {
     SpatialRoute route;
@@ -192,7 +241,10 @@ static SpatialRoute spatial_route_library(const fvb_config *cfg, int kind)
     if (cfg->params_ext || name.empty() || !find_wave_body(name))
         return route;
     if (kind != FVB_SPNZ_WHITE)
-        return spatial_route_library_noise(cfg, kind, name);
+    {
+        route = spatial_route_library_noise(cfg, kind, name);
+        return route.found() ? route : spatial_route_library_wave_noise(cfg, kind, name);
+    }
     if (!DeviceRegistry<fvb_device_spatial_model>::instance().find(name, cfg->n_params, &entry))
         return spatial_route_library_wave(cfg, name);
     SpatialKernels k = get_spatial_kernels_linear(cfg->n_params, cfg->need_f != 0);
@@ -341,6 +393,27 @@ int fvb_spatial_run::open(const fvb_config *cfg_, const fvb_spatial *sp_, const 
 // launched with; upload_plan() adds the rest.
 int fvb_spatial_run::start_setup(const void *d_data, const fvb_outputs *d_out)
 {
+    if (k.wave && cfg.n_phis > 1)
+    {
+        // the state image with every class's statistics (46 KB per voxel at 32 parameters and 8 precisions): worked out
+        // before the run, a device that cannot hold it says so instead of failing inside the allocation
+        const size_t bytes = sizeof(double) * (size_t)k.state_rows * (size_t)V;
+        size_t free_bytes = 0, total_bytes = 0;
+        FVB_HIP_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
+        // (what the engine's pool keeps from earlier runs is not free to the driver, but it is to this allocation)
+        uint64_t reserved = 0, used = 0;
+        if (hipMemPool_t pool = fvb::api_pool())
+            if (hipMemPoolGetAttribute(pool, hipMemPoolAttrReservedMemCurrent, &reserved) == hipSuccess
+                && hipMemPoolGetAttribute(pool, hipMemPoolAttrUsedMemCurrent, &used) == hipSuccess && reserved > used)
+                free_bytes += (size_t)(reserved - used);
+        (void)hipGetLastError();
+        if (bytes > free_bytes)
+            return api_fail(-40, "spatial VB with " + std::to_string(P) + " parameters and " + std::to_string(cfg.n_phis)
+                    + " noise precisions keeps " + std::to_string(k.state_rows) + " rows per voxel: " + std::to_string(bytes >> 20) + " MiB for "
+                    + std::to_string(V) + " voxels, the device has " + std::to_string(free_bytes >> 20) + " MiB free");
+        if (k.wave_lds > 64 * 1024) // (more dynamic LDS than a kernel gets without asking; the library's launcher asks for its own)
+            FVB_HIP_CHECK(hipFuncSetAttribute((const void *)k.theta, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.wave_lds));
+    }
     FVB_HIP_CHECK(d_state.alloc(sizeof(double) * (size_t)k.state_rows * V, stream));
     FVB_HIP_CHECK(d_status.alloc(sizeof(int32_t) * (size_t)V, stream));
     memset(&sa, 0, sizeof(sa));
@@ -1077,6 +1150,31 @@ const char *fabber_vb_device_spatial_wave_model_name(int32_t i)
 int32_t fabber_vb_find_device_spatial_wave_model(const char *name, fvb_device_spatial_wave_model *entry)
 {
     return (name && entry && DeviceRegistry<fvb_device_spatial_wave_model>::instance().find(name, 0, entry)) ? 1 : 0;
+}
+
+int32_t fabber_vb_register_device_spatial_wave_noise_model(const fvb_device_spatial_wave_noise_model *model)
+{
+    return DeviceRegistry<fvb_device_spatial_wave_noise_model>::instance().add(model);
+}
+
+int32_t fabber_vb_unregister_device_spatial_wave_noise_model(const char *name)
+{
+    return DeviceRegistry<fvb_device_spatial_wave_noise_model>::instance().remove(name, 0);
+}
+
+int32_t fabber_vb_device_spatial_wave_noise_model_count(void)
+{
+    return DeviceRegistry<fvb_device_spatial_wave_noise_model>::instance().count();
+}
+
+const char *fabber_vb_device_spatial_wave_noise_model_name(int32_t i)
+{
+    return DeviceRegistry<fvb_device_spatial_wave_noise_model>::instance().name(i);
+}
+
+int32_t fabber_vb_find_device_spatial_wave_noise_model(const char *name, fvb_device_spatial_wave_noise_model *entry)
+{
+    return (name && entry && DeviceRegistry<fvb_device_spatial_wave_noise_model>::instance().find(name, 0, entry)) ? 1 : 0;
 }
 
 // (the selection function of the run: "" where open() would answer -40 or -44)

@@ -57,18 +57,49 @@ FVB_HD SpWideLayout sp_wide_layout(int P)
     return L;
 }
 
+// Under a noise pattern (N = 2 ... FVB_MAX_PHIS precisions) the statistics of every class follow the rows above, in the
+// order of SpPattern<P, N> (vb_spatial_noise.h): b_k, c_k, A_k, u_k, s_k. The rows B, C, A, U, S above are not used then;
+// the a_K kernels read M and SIG only and work on either image.
+struct SpWideClassRows
+{
+    int NB, NC, AK, UK, SK, ROWS;
+};
+
+FVB_HD SpWideClassRows sp_wide_class_rows(int P, int N)
+{
+    const SpWideLayout S = sp_wide_layout(P);
+    SpWideClassRows R;
+    R.NB = S.ROWS;
+    R.NC = R.NB + N;
+    R.AK = R.NC + N;
+    R.UK = R.AK + N * S.PT;
+    R.SK = R.UK + N * P;
+    R.ROWS = R.SK + N;
+    return R;
+}
+
+// rows of the state image: 5 724 at P = 32, N = 8 (46 KB per voxel)
+FVB_HD int sp_wide_state_rows(int P, int N)
+{
+    return N > 1 ? sp_wide_class_rows(P, N).ROWS : sp_wide_layout(P).ROWS;
+}
+
 // timepoints of J staged in LDS at a time (one per lane where a pass works on timepoints)
 constexpr int SPW_TC = 64;
+// N > 1: the chunk's unmasked timepoints listed class by class (spw_class_lists), SPW_TC + 16 int32
+constexpr int SPW_CLASS_LIST_DOUBLES = (SPW_TC + 16) / 2;
 
-// LDS of one voxel, in doubles: the WaveLayout fields the shared wave functions read (one noise precision), a chunk of
-// J [SPW_TC][Ps] and its residuals, a row of per-timepoint terms and 3 P doubles of per-parameter terms (pv). The
-// other fields of WaveLayout are not used here. At P = 32: 40.9 KB.
-FVB_HD WaveLayout sp_wave_layout(int P)
+// LDS of one voxel, in doubles: the WaveLayout fields the shared wave functions read, a chunk of J [SPW_TC][Ps] and its
+// residuals, a row of per-timepoint terms and 3 P doubles of per-parameter terms (pv). The other fields of WaveLayout
+// are not used here. At P = 32: 40.9 KB. With N > 1 noise precisions A, u, s, kq, trs, cnt, b, c are N-fold, where the
+// shared wave functions index them (L.A + phi * PT, L.u + phi * P, L.s + phi ...), and the class lists of a chunk follow
+// Sig (field z); with N = 1 every offset and the size are those of the one-precision layout. At P = 32, N = 8: 72.9 KB.
+FVB_HD WaveLayout sp_wave_layout(int P, int N = 1)
 {
     WaveLayout L = {};
     L.T = SPW_TC;
     L.P = P;
-    L.N = 1;
+    L.N = N;
     L.Ps = P | 1; // odd row stride: lanes reading one column of consecutive rows hit distinct banks
     L.PT = P * (P + 1) / 2;
     L.PP = P * P;
@@ -80,14 +111,14 @@ FVB_HD WaveLayout sp_wave_layout(int P)
     FVB_WL(r, SPW_TC)
     FVB_WL(part, 64)
     FVB_WL(pv, 3 * P)
-    FVB_WL(A, L.PT)
-    FVB_WL(u, P)
-    FVB_WL(s, 1)
-    FVB_WL(kq, 1)
-    FVB_WL(trs, 1)
-    FVB_WL(cnt, 1)
-    FVB_WL(b, 1)
-    FVB_WL(c, 1)
+    FVB_WL(A, N * L.PT)
+    FVB_WL(u, N * P)
+    FVB_WL(s, N)
+    FVB_WL(kq, N)
+    FVB_WL(trs, N)
+    FVB_WL(cnt, N)
+    FVB_WL(b, N)
+    FVB_WL(c, N)
     FVB_WL(m, P)
     FVB_WL(ml, P)
     FVB_WL(pm, P)
@@ -95,6 +126,7 @@ FVB_HD WaveLayout sp_wave_layout(int P)
     FVB_WL(rhs, P)
     FVB_WL(Lam, L.PP)
     FVB_WL(Sig, L.PP)
+    FVB_WL(z, N > 1 ? SPW_CLASS_LIST_DOUBLES : 0)
 #undef FVB_WL
     L.n_doubles = o;
     L.bytes = sizeof(double) * (size_t)o;
@@ -131,23 +163,42 @@ __device__ __forceinline__ void spw_load(const SpatialArgs &sa, WaveCtx &cx)
     const size_t V = cx.V;
     const double *p = sa.state + cx.v;
     double *sh = cx.sh;
+    const bool classes = L.N > 1; // (the statistics are the class rows' then)
     FVB_WAVE_FOR(i, P)
     {
         sh[L.m + i] = p[(size_t)(S.M + i) * V];
         sh[L.pm + i] = p[(size_t)(S.PM + i) * V];
         sh[L.pprec + i] = p[(size_t)(S.PPREC + i) * V];
-        sh[L.u + i] = p[(size_t)(S.U + i) * V];
+        if (!classes)
+            sh[L.u + i] = p[(size_t)(S.U + i) * V];
         sh[L.ml + i] = p[(size_t)(S.ML + i) * V];
     }
     FVB_WAVE_FOR(e, L.PP)
     sh[L.Sig + e] = p[(size_t)(S.SIG + tri(e / P, e % P)) * V];
-    FVB_WAVE_FOR(e, L.PT)
-    sh[L.A + e] = p[(size_t)(S.A + e) * V];
-    if (cx.lane == 0)
+    if (classes)
     {
-        sh[L.b] = p[(size_t)S.B * V];
-        sh[L.c] = p[(size_t)S.C * V];
-        sh[L.s] = p[(size_t)S.S * V];
+        const SpWideClassRows R = sp_wide_class_rows(P, L.N);
+        FVB_WAVE_FOR(e, L.N * L.PT)
+        sh[L.A + e] = p[(size_t)(R.AK + e) * V];
+        FVB_WAVE_FOR(e, L.N * P)
+        sh[L.u + e] = p[(size_t)(R.UK + e) * V];
+        FVB_WAVE_FOR(k, L.N)
+        {
+            sh[L.b + k] = p[(size_t)(R.NB + k) * V];
+            sh[L.c + k] = p[(size_t)(R.NC + k) * V];
+            sh[L.s + k] = p[(size_t)(R.SK + k) * V];
+        }
+    }
+    else
+    {
+        FVB_WAVE_FOR(e, L.PT)
+        sh[L.A + e] = p[(size_t)(S.A + e) * V];
+        if (cx.lane == 0)
+        {
+            sh[L.b] = p[(size_t)S.B * V];
+            sh[L.c] = p[(size_t)S.C * V];
+            sh[L.s] = p[(size_t)S.S * V];
+        }
     }
     cx.logdetLam = p[(size_t)S.LOGDET * V];
     cx.covValid = true;
@@ -191,6 +242,23 @@ __device__ __forceinline__ void spw_store_noise(const SpatialArgs &sa, WaveCtx &
     const size_t V = cx.V;
     double *p = sa.state + cx.v;
     const double *sh = cx.sh;
+    if (L.N > 1)
+    {
+        const SpWideClassRows R = sp_wide_class_rows(P, L.N);
+        FVB_WAVE_FOR(i, P)
+        p[(size_t)(S.ML + i) * V] = sh[L.ml + i];
+        FVB_WAVE_FOR(e, L.N * L.PT)
+        p[(size_t)(R.AK + e) * V] = sh[L.A + e];
+        FVB_WAVE_FOR(e, L.N * P)
+        p[(size_t)(R.UK + e) * V] = sh[L.u + e];
+        FVB_WAVE_FOR(k, L.N)
+        {
+            p[(size_t)(R.NB + k) * V] = sh[L.b + k];
+            p[(size_t)(R.NC + k) * V] = sh[L.c + k];
+            p[(size_t)(R.SK + k) * V] = sh[L.s + k];
+        }
+        return;
+    }
     FVB_WAVE_FOR(i, P)
     {
         p[(size_t)(S.U + i) * V] = sh[L.u + i];
@@ -237,7 +305,7 @@ __device__ __forceinline__ void spw_stage_chunk(const KernelArgs &ka, WaveCtx &c
 // Where the set-up kernel and the second sweep take the model's linearisation from, chunk by chunk - what they are
 // templates on (Rows):
 //   Rows(sa, v, next)    voxel v's source; next = false: the linearisation the moments in the state belong to
-//   layout(P)            the LDS layout of the kernels built around the source (sp_wave_layout, or an extension of it)
+//   layout(P, N)         the LDS layout of the kernels built around the source (sp_wave_layout, or an extension of it)
 //   centre(ka, cx)       once before the chunks of a pass: the linearisation is about the centre in L.ml
 //   chunk(ka, cx, phi_index, t0, n, bad_offset, bad_jac)    spw_stage_chunk's contract for the chunk [t0, t0 + n)
 // SpwHostRows: the rows the host computed (HostLin of vb_spatial_api.hip). vb_spatial_wave_model.h has the source that
@@ -249,9 +317,9 @@ struct SpwHostRows
         : lin((next ? sa.lin_next : sa.lin_cur) + (size_t)v * sa.ka.cfg.n_times * (sa.ka.cfg.n_params + 1))
     {
     }
-    static __device__ __forceinline__ WaveLayout layout(int P)
+    static __device__ __forceinline__ WaveLayout layout(int P, int N = 1)
     {
-        return sp_wave_layout(P);
+        return sp_wave_layout(P, N);
     }
     __device__ __forceinline__ void centre(const KernelArgs &, WaveCtx &) const
     {
@@ -344,17 +412,18 @@ __device__ __forceinline__ int spw_moments(const KernelArgs &ka, WaveCtx &cx, co
     return any_offset ? FVB_BAD_OFFSET : (any_jac ? FVB_BAD_JACOBIAN : FVB_OK);
 }
 
-// tr(Sigma J'J) (noisemodel_white.cc:252,417): a row sum per lane, the rows added in order by every lane
-__device__ __forceinline__ double spw_trace_SA(WaveCtx &cx)
+// tr(Sigma J'J) (noisemodel_white.cc:252,417): a row sum per lane, the rows added in order by every lane. k: the noise
+// class whose moments are meant (the only one, 0, under one precision)
+__device__ __forceinline__ double spw_trace_SA(WaveCtx &cx, int k = 0)
 {
     const WaveLayout &L = cx.L;
-    const int P = L.P;
+    const int P = L.P, Ak = L.A + k * L.PT;
     double *sh = cx.sh;
     FVB_WAVE_FOR(i, P)
     {
         double s = 0;
         for (int j = 0; j < P; j++)
-            s += sh[L.Sig + i * P + j] * sh[L.A + tri(i, j)];
+            s += sh[L.Sig + i * P + j] * sh[Ak + tri(i, j)];
         sh[L.pv + i] = s;
     }
     wave_sync();
@@ -366,10 +435,11 @@ __device__ __forceinline__ double spw_trace_SA(WaveCtx &cx)
 }
 
 // k'k from the moments, k'k = s - 2 d'u + d'A d with d = m - ml, and tr(Sigma A) (residual_terms): what F "theta" reads
-__device__ __forceinline__ void spw_moment_residual(WaveCtx &cx, double &kk, double &trSA)
+// (k: the noise class, as spw_trace_SA)
+__device__ __forceinline__ void spw_moment_residual(WaveCtx &cx, double &kk, double &trSA, int k = 0)
 {
     const WaveLayout &L = cx.L;
-    const int P = L.P;
+    const int P = L.P, Ak = L.A + k * L.PT, uk = L.u + k * P;
     double *sh = cx.sh;
     FVB_WAVE_FOR(i, P)
     {
@@ -377,10 +447,10 @@ __device__ __forceinline__ void spw_moment_residual(WaveCtx &cx, double &kk, dou
         double dA = 0, tr = 0;
         for (int j = 0; j < P; j++)
         {
-            dA += sh[L.A + tri(i, j)] * (sh[L.m + j] - sh[L.ml + j]);
-            tr += sh[L.Sig + i * P + j] * sh[L.A + tri(i, j)];
+            dA += sh[Ak + tri(i, j)] * (sh[L.m + j] - sh[L.ml + j]);
+            tr += sh[L.Sig + i * P + j] * sh[Ak + tri(i, j)];
         }
-        sh[L.pv + i] = di * sh[L.u + i];
+        sh[L.pv + i] = di * sh[uk + i];
         sh[L.pv + P + i] = di * dA;
         sh[L.pv + 2 * P + i] = tr;
     }
@@ -393,7 +463,7 @@ __device__ __forceinline__ void spw_moment_residual(WaveCtx &cx, double &kk, dou
         dAd += sh[L.pv + P + i];
         trSA += sh[L.pv + 2 * P + i];
     }
-    kk = sh[L.s] - 2 * du + dAd;
+    kk = sh[L.s + k] - 2 * du + dAd;
     wave_sync();
 }
 
@@ -431,6 +501,172 @@ __device__ __forceinline__ double spw_direct_residual(const KernelArgs &ka, Wave
     return kk;
 }
 
+// ---- N > 1 noise precisions (noise-pattern, noisemodel_white.cc:166-273): the sums over t class by class -----------------
+// The class of a timepoint is the same for every voxel, so the chunk's unmasked timepoints are listed class by class once
+// per chunk (in LDS: ord [SPW_TC], the lists one after another in order of t; cst [N + 1], where each begins) and every
+// sum over the timepoints of a class walks its list. The partial sums are carried in the LDS class areas between chunks:
+// no accumulator is indexed by a class. Masked timepoints are in no list.
+__device__ __forceinline__ void spw_class_lists(const KernelArgs &ka, WaveCtx &cx, int t0, int n)
+{
+    const WaveLayout &L = cx.L;
+    int *ord = (int *)(cx.sh + L.z), *cst = ord + SPW_TC;
+    const int lane = cx.lane;
+    const int mine = (lane < n) ? (ka.cfg.phi_index ? (int)ka.cfg.phi_index[t0 + lane] : 0) : 255;
+    int start = 0;
+    for (int k = 0; k < L.N; k++)
+    {
+        const unsigned long long in_k = __ballot(mine == k);
+        if (mine == k) // (start + rank < n <= SPW_TC)
+            ord[start + __popcll(in_k & ((1ull << lane) - 1ull))] = lane;
+        if (lane == 0)
+            cst[k] = start;
+        start += __popcll(in_k);
+    }
+    if (lane == 0)
+        cst[L.N] = start;
+    wave_sync();
+}
+
+// spw_moments per class: A_k = J'Q_k J, u_k = J'Q_k r, s_k = r'Q_k r, each a sum over the class's timepoints in order
+template <class Rows>
+__device__ __forceinline__ int spw_moments_classes(const KernelArgs &ka, WaveCtx &cx, const Rows &rows)
+{
+    const WaveLayout &L = cx.L;
+    const int T = ka.cfg.n_times, P = L.P, Ps = L.Ps, PT = L.PT, N = L.N;
+    const int E = PT + P + 1;
+    double *sh = cx.sh;
+    const int *ord = (const int *)(sh + L.z), *cst = ord + SPW_TC;
+    const uint8_t *phi_index = (ka.n_unmasked == T) ? nullptr : ka.cfg.phi_index;
+    FVB_WAVE_FOR(e, N * PT)
+    sh[L.A + e] = 0;
+    FVB_WAVE_FOR(e, N * P)
+    sh[L.u + e] = 0;
+    FVB_WAVE_FOR(k, N)
+    sh[L.s + k] = 0;
+    wave_sync();
+    // this lane's entries e = lane + 64 k, as spw_moments has them: the product x[t] y[t] of two columns of the staged
+    // chunk (a column of J with stride Ps, or r), and where the entry of class 0 lies with the step to the next class
+    int xa[SPW_MAX_SLOTS], xb[SPW_MAX_SLOTS], dst[SPW_MAX_SLOTS];
+#pragma unroll
+    for (int k = 0; k < SPW_MAX_SLOTS; k++)
+    {
+        const int e = cx.lane + 64 * k;
+        xa[k] = xb[k] = L.r;
+        dst[k] = -1; // none
+        if (e < PT)
+        {
+            int a = 0;
+            while ((a + 1) * (a + 2) / 2 <= e)
+                a++;
+            xa[k] = L.J + a;
+            xb[k] = L.J + e - a * (a + 1) / 2;
+            dst[k] = L.A + e;
+        }
+        else if (e < PT + P)
+        {
+            xa[k] = L.J + e - PT;
+            dst[k] = L.u + e - PT;
+        }
+        else if (e == E - 1)
+            dst[k] = L.s;
+    }
+    bool bad_offset = false, bad_jac = false;
+    rows.centre(ka, cx);
+    for (int t0 = 0; t0 < T; t0 += SPW_TC)
+    {
+        const int n = (T - t0 < SPW_TC) ? T - t0 : SPW_TC;
+        rows.chunk(ka, cx, phi_index, t0, n, bad_offset, bad_jac);
+        spw_class_lists(ka, cx, t0, n);
+#pragma unroll
+        for (int k = 0; k < SPW_MAX_SLOTS; k++)
+        {
+            if (dst[k] < 0)
+                continue;
+            const int e = cx.lane + 64 * k;
+            const int sa_ = (xa[k] == L.r) ? 1 : Ps, sb_ = (xb[k] == L.r) ? 1 : Ps;
+            const int step = (e < PT) ? PT : ((e < PT + P) ? P : 1);
+            for (int c = 0; c < N; c++)
+            {
+                const int q0 = cst[c], q1 = cst[c + 1];
+                if (q0 == q1)
+                    continue;
+                double acc = sh[dst[k] + c * step];
+                for (int q = q0; q < q1; q++)
+                {
+                    const int t = ord[q];
+                    acc += sh[xa[k] + t * sa_] * sh[xb[k] + t * sb_];
+                }
+                sh[dst[k] + c * step] = acc;
+            }
+        }
+        wave_sync(); // (the next chunk overwrites the staged one and its lists)
+    }
+    const bool any_offset = __any(bad_offset), any_jac = __any(bad_jac);
+    return any_offset ? FVB_BAD_OFFSET : (any_jac ? FVB_BAD_JACOBIAN : FVB_OK);
+}
+
+// spw_direct_residual per class into L.kq: lane k carries the sum of class k from chunk to chunk
+template <class Rows>
+__device__ __forceinline__ void spw_direct_residual_classes(const KernelArgs &ka, WaveCtx &cx, const Rows &rows)
+{
+    const WaveLayout &L = cx.L;
+    const int T = ka.cfg.n_times, P = L.P, Ps = L.Ps, N = L.N;
+    double *sh = cx.sh;
+    const int *ord = (const int *)(sh + L.z), *cst = ord + SPW_TC;
+    const uint8_t *phi_index = (ka.n_unmasked == T) ? nullptr : ka.cfg.phi_index;
+    FVB_WAVE_FOR(i, P)
+    sh[L.pv + i] = sh[L.ml + i] - sh[L.m + i];
+    bool bad_offset = false, bad_jac = false; // (the set-up or the previous re-centre has reported these already)
+    double kk = 0;
+    rows.centre(ka, cx);
+    for (int t0 = 0; t0 < T; t0 += SPW_TC)
+    {
+        const int n = (T - t0 < SPW_TC) ? T - t0 : SPW_TC;
+        rows.chunk(ka, cx, phi_index, t0, n, bad_offset, bad_jac);
+        spw_class_lists(ka, cx, t0, n);
+        FVB_WAVE_FOR(t, n)
+        {
+            double Jd = 0;
+            for (int i = 0; i < P; i++)
+                Jd += sh[L.J + t * Ps + i] * sh[L.pv + i];
+            const double k = sh[L.r + t] + Jd;
+            sh[L.part + t] = k * k;
+        }
+        wave_sync();
+        if (cx.lane < N)
+            for (int q = cst[cx.lane]; q < cst[cx.lane + 1]; q++)
+                kk += sh[L.part + ord[q]];
+        wave_sync();
+    }
+    if (cx.lane < N)
+        sh[L.kq + cx.lane] = kk;
+    wave_sync();
+}
+
+// tr(Sigma A_k) of every class into L.trs, and the class counts (the trace of Q_k) into L.cnt
+__device__ __forceinline__ void spw_class_traces(const SpatialArgs &sa, WaveCtx &cx)
+{
+    const WaveLayout &L = cx.L;
+    for (int k = 0; k < L.N; k++)
+    {
+        const double tr = spw_trace_SA(cx, k);
+        if (cx.lane == 0)
+        {
+            cx.sh[L.trs + k] = tr;
+            cx.sh[L.cnt + k] = sa.nz_count[k];
+        }
+    }
+    wave_sync();
+}
+
+// the residual at the linearisation centre, k'Q_k k = s_k
+__device__ __forceinline__ void spw_class_residual_at_centre(WaveCtx &cx)
+{
+    FVB_WAVE_FOR(k, cx.L.N)
+    cx.sh[cx.L.kq + k] = cx.sh[cx.L.s + k];
+    wave_sync();
+}
+
 // the free energy's residual terms (one noise precision) into LDS for wave_free_energy / wave_update_noise
 __device__ __forceinline__ void spw_set_residual(const KernelArgs &ka, WaveCtx &cx, double kk, double trSA)
 {
@@ -444,7 +680,8 @@ __device__ __forceinline__ void spw_set_residual(const KernelArgs &ka, WaveCtx &
 }
 
 // ---- setup: Vb::SetupPerVoxelDists (inference_vb.cc:207-247), one workgroup per voxel ------------------------------
-template <class Rows>
+// CLASSES: the form for N = cfg.n_phis > 1 noise precisions (class rows of the state image, N-fold LDS class areas)
+template <class Rows, bool CLASSES = false>
 __device__ __forceinline__ void spw_setup(const SpatialArgs &sa)
 {
     const KernelArgs &ka = sa.ka;
@@ -453,20 +690,32 @@ __device__ __forceinline__ void spw_setup(const SpatialArgs &sa)
     if (v >= ka.cfg.n_voxels)
         return;
     const int P = ka.cfg.n_params;
+    const int N = CLASSES ? ka.cfg.n_phis : 1;
     WaveCtx cx;
-    spw_init_ctx(cx, v, V, Rows::layout(P));
+    spw_init_ctx(cx, v, V, Rows::layout(P, N));
     const WaveLayout &L = cx.L;
     const SpWideLayout S = sp_wide_layout(P);
     double *sh = cx.sh;
     if (ka.cfg.init_mvn)
     {
-        const int n = P + 1, nCov = n * (n + 1) / 2;
+        const int n = P + N, nCov = n * (n + 1) / 2;
         const double *src = ka.cfg.init_mvn + v;
         FVB_WAVE_FOR(e, L.PP)
         sh[L.Sig + e] = src[(size_t)tri(e / P, e % P) * V];
         FVB_WAVE_FOR(i, P)
         sh[L.m + i] = src[(size_t)(nCov + i) * V];
-        if (cx.lane == 0)
+        if (CLASSES)
+        {
+            FVB_WAVE_FOR(k, N) // WhiteParams::InputFromMVN, noisemodel_white.cc:70-79
+            {
+                const double nm = src[(size_t)(nCov + P + k) * V];
+                const double nv = src[(size_t)tri(P + k, P + k) * V];
+                const double b = nv / nm;
+                sh[L.b + k] = b;
+                sh[L.c + k] = nm / b;
+            }
+        }
+        else if (cx.lane == 0)
         {
             const double nm = src[(size_t)(nCov + P) * V];
             const double nv = src[(size_t)tri(P, P) * V];
@@ -487,7 +736,15 @@ __device__ __forceinline__ void spw_setup(const SpatialArgs &sa)
             sh[L.m + i] = to_fabber(tr, mean);
             sh[L.Sig + i * P + i] = to_fabber_var(tr, ka.cfg.post_var[i]);
         }
-        if (cx.lane == 0)
+        if (CLASSES)
+        {
+            FVB_WAVE_FOR(k, N)
+            {
+                sh[L.b + k] = ka.cfg.noise_post_b[k];
+                sh[L.c + k] = ka.cfg.noise_post_c[k];
+            }
+        }
+        else if (cx.lane == 0)
         {
             sh[L.b] = ka.cfg.noise_post_b[0];
             sh[L.c] = ka.cfg.noise_post_c[0];
@@ -502,7 +759,7 @@ __device__ __forceinline__ void spw_setup(const SpatialArgs &sa)
     }
     wave_sync();
     cx.logdetLam = 0;
-    const int status = spw_moments(ka, cx, Rows(sa, v, true));
+    const int status = CLASSES ? spw_moments_classes(ka, cx, Rows(sa, v, true)) : spw_moments(ka, cx, Rows(sa, v, true));
     if (cx.lane == 0)
         sa.status[v] = status ? (status | 0x100) : 0;
     spw_store_theta(sa, cx);
@@ -743,7 +1000,7 @@ __device__ __forceinline__ double spw_apply_priors(const SpatialArgs &sa, WaveCt
 }
 
 // ---- first sweep, one level: priors + UpdateTheta (inference_vb.cc:614-672), one workgroup per voxel of the level ----
-template <bool NEEDF>
+template <bool NEEDF, bool CLASSES = false>
 __global__ __launch_bounds__(64) void vb_spatial_wave_theta_kernel(const SpatialArgs *__restrict__ sap, int level_begin,
     int level_count, int it)
 {
@@ -758,7 +1015,7 @@ __global__ __launch_bounds__(64) void vb_spatial_wave_theta_kernel(const Spatial
     if (ignored && v != sa.owned_end - 1)
         return;
     WaveCtx cx;
-    spw_init_ctx(cx, v, (size_t)ka.cfg.n_voxels, sp_wave_layout(ka.cfg.n_params));
+    spw_init_ctx(cx, v, (size_t)ka.cfg.n_voxels, sp_wave_layout(ka.cfg.n_params, CLASSES ? ka.cfg.n_phis : 1));
     spw_load(sa, cx);
     const double Fprior = spw_apply_priors(sa, cx, it);
     if (v == sa.owned_end - 1 && cx.lane == 0)
@@ -767,7 +1024,13 @@ __global__ __launch_bounds__(64) void vb_spatial_wave_theta_kernel(const Spatial
         return;
     if (NEEDF) // F "before" (:643): the means are still the linearisation centre, k'k = s
     {
-        spw_set_residual(ka, cx, cx.sh[cx.L.s], spw_trace_SA(cx));
+        if (CLASSES)
+        {
+            spw_class_traces(sa, cx);
+            spw_class_residual_at_centre(cx);
+        }
+        else
+            spw_set_residual(ka, cx, cx.sh[cx.L.s], spw_trace_SA(cx));
         double F;
         bool finite = true;
         const bool ok = wave_free_energy(ka, cx, Fprior, F, finite);
@@ -784,8 +1047,24 @@ __global__ __launch_bounds__(64) void vb_spatial_wave_theta_kernel(const Spatial
     if (NEEDF && status == FVB_OK) // F "theta" (:651)
     {
         double kk, trSA;
-        spw_moment_residual(cx, kk, trSA);
-        spw_set_residual(ka, cx, kk, trSA);
+        if (CLASSES)
+        {
+            for (int k = 0; k < cx.L.N; k++) // s_k - 2 d'u_k + d'A_k d and tr(Sigma A_k); L.cnt is F "before"'s
+            {
+                spw_moment_residual(cx, kk, trSA, k);
+                if (cx.lane == 0)
+                {
+                    cx.sh[cx.L.kq + k] = kk;
+                    cx.sh[cx.L.trs + k] = trSA;
+                }
+            }
+            wave_sync();
+        }
+        else
+        {
+            spw_moment_residual(cx, kk, trSA);
+            spw_set_residual(ka, cx, kk, trSA);
+        }
         double F;
         bool finite = true;
         const bool ok = wave_free_energy(ka, cx, Fprior, F, finite);
@@ -798,7 +1077,7 @@ __global__ __launch_bounds__(64) void vb_spatial_wave_theta_kernel(const Spatial
 }
 
 // ---- second sweep: UpdateNoise, ReCentre, F (inference_vb.cc:674-722), one workgroup per owned voxel ----------------
-template <class Rows, bool NEEDF>
+template <class Rows, bool NEEDF, bool CLASSES = false>
 __device__ __forceinline__ void spw_noise(const SpatialArgs &sa)
 {
     const KernelArgs &ka = sa.ka;
@@ -809,14 +1088,23 @@ __device__ __forceinline__ void spw_noise(const SpatialArgs &sa)
         return;
     const int P = ka.cfg.n_params;
     WaveCtx cx;
-    spw_init_ctx(cx, v, (size_t)ka.cfg.n_voxels, Rows::layout(P));
+    spw_init_ctx(cx, v, (size_t)ka.cfg.n_voxels, Rows::layout(P, CLASSES ? ka.cfg.n_phis : 1));
     spw_load(sa, cx);
     const WaveLayout &L = cx.L;
     double *sh = cx.sh;
     // the residual about the centre the moments belong to ...
-    double kk = spw_direct_residual(ka, cx, Rows(sa, v, false));
-    double trSA = spw_trace_SA(cx);
-    spw_set_residual(ka, cx, kk, trSA);
+    double kk = 0, trSA = 0;
+    if (CLASSES) // (per class, in L.kq / L.trs / L.cnt)
+    {
+        spw_direct_residual_classes(ka, cx, Rows(sa, v, false));
+        spw_class_traces(sa, cx);
+    }
+    else
+    {
+        kk = spw_direct_residual(ka, cx, Rows(sa, v, false));
+        trSA = spw_trace_SA(cx);
+        spw_set_residual(ka, cx, kk, trSA);
+    }
     wave_update_noise(ka, cx);
     // ... and the re-centre about the means of this iteration's first sweep
     int status = FVB_OK;
@@ -825,15 +1113,25 @@ __device__ __forceinline__ void spw_noise(const SpatialArgs &sa)
         FVB_WAVE_FOR(i, P)
         sh[L.ml + i] = sh[L.m + i];
         wave_sync();
-        status = spw_moments(ka, cx, Rows(sa, v, true));
-        kk = sh[L.s]; // the centre is the mean now: k = y - g
-        trSA = spw_trace_SA(cx);
+        if (CLASSES)
+        {
+            status = spw_moments_classes(ka, cx, Rows(sa, v, true));
+            spw_class_residual_at_centre(cx);
+            spw_class_traces(sa, cx);
+        }
+        else
+        {
+            status = spw_moments(ka, cx, Rows(sa, v, true));
+            kk = sh[L.s]; // the centre is the mean now: k = y - g
+            trSA = spw_trace_SA(cx);
+        }
     }
     if (status == FVB_OK && NEEDF)
     {
         // only the last of the four F evaluations per iteration is observable; it uses the prior term of the LAST
         // voxel of the first sweep (inference_vb.cc:612,689,702)
-        spw_set_residual(ka, cx, kk, trSA);
+        if (!CLASSES)
+            spw_set_residual(ka, cx, kk, trSA);
         cx.covValid = true;
         cx.precValid = false;
         double F;
@@ -866,18 +1164,35 @@ __global__ __launch_bounds__(256) void vb_spatial_wide_pack_kernel(const Spatial
     const int P = ka.cfg.n_params;
     const SpWideLayout S = sp_wide_layout(P);
     const size_t V = (size_t)ka.cfg.n_voxels;
-    const int n = P + 1, nCov = n * (n + 1) / 2;
+    // (N > 1 precisions in this family: white noise under a pattern, the class rows of the state image)
+    const int N = (ka.cfg.noise == FVB_NOISE_WHITE && ka.cfg.n_phis > 1) ? ka.cfg.n_phis : 1;
+    const int n = P + N, nCov = n * (n + 1) / 2;
     const double *p = sa.state + v;
     double *dst = ka.out.mvn + v;
     for (int i = 0; i < S.PT; i++)
         dst[(size_t)i * V] = p[(size_t)(S.SIG + i) * V];
-    for (int j = 0; j < P; j++)
-        dst[(size_t)tri(P, j) * V] = 0.0;
-    const double b = p[(size_t)S.B * V], c = p[(size_t)S.C * V];
-    dst[(size_t)tri(P, P) * V] = b * b * c;
     for (int i = 0; i < P; i++)
         dst[(size_t)(nCov + i) * V] = p[(size_t)(S.M + i) * V];
-    dst[(size_t)(nCov + P) * V] = b * c;
+    if (N > 1) // noisemodel_white.cc:55-68, in the order of SpPattern's pack_noise
+    {
+        const SpWideClassRows R = sp_wide_class_rows(P, N);
+        for (int k = 0; k < N; k++)
+        {
+            const double b = p[(size_t)(R.NB + k) * V], c = p[(size_t)(R.NC + k) * V];
+            for (int j = 0; j < P + k; j++)
+                dst[(size_t)tri(P + k, j) * V] = 0.0;
+            dst[(size_t)tri(P + k, P + k) * V] = b * b * c;
+            dst[(size_t)(nCov + P + k) * V] = b * c;
+        }
+    }
+    else
+    {
+        for (int j = 0; j < P; j++)
+            dst[(size_t)tri(P, j) * V] = 0.0;
+        const double b = p[(size_t)S.B * V], c = p[(size_t)S.C * V];
+        dst[(size_t)tri(P, P) * V] = b * b * c;
+        dst[(size_t)(nCov + P) * V] = b * c;
+    }
     dst[(size_t)(nCov + n) * V] = 1.0;
     if (ka.out.status)
         ka.out.status[v] = sa.status[v];

@@ -39,6 +39,22 @@ SpatialKernels get_spatial_kernels_wave_model(int P, bool need_f)
     k.wave_lds = sp_wave_model_layout(P).bytes;
     return k;
 }
+// ... and under a noise pattern of N = 2 ... FVB_MAX_PHIS precisions (include/fabber_device_spatial_wave_noise_model.h):
+// the first sweep in its form for N classes, the state image with the class rows, the LDS of the layout for (P, N)
+SpatialKernels get_spatial_kernels_wave_noise_model(int P, int N, bool need_f)
+{
+    SpatialKernels k = get_spatial_kernels_wave_model(P, need_f);
+    if (!k.theta || N < 2 || N > FVB_MAX_PHIS)
+        return SpatialKernels{};
+    k.theta = need_f ? (SpatialThetaFn)vb_spatial_wave_theta_kernel<true, true> : (SpatialThetaFn)vb_spatial_wave_theta_kernel<false, true>;
+    k.state_rows = sp_wide_state_rows(P, N);
+    k.wave_lds = sp_wave_model_layout(P, N).bytes;
+    return k;
+}
+uint32_t spatial_wave_noise_model_lds_probe()
+{
+    return (uint32_t)sp_wave_model_layout(FVB_MAX_PARAMS, FVB_MAX_PHIS).n_doubles;
+}
 // what a library's entry must report as its lds_probe and as its wave_layout_size
 uint32_t spatial_wave_model_lds_probe()
 {

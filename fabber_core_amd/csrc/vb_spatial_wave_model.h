@@ -17,6 +17,10 @@
  * doubles of rden (sp_wave_model_layout): 57.8 KB at P = 32. All lanes of the wavefront read the SAME vector entry in an
  * evaluation (they differ in t): a broadcast, no bank conflict whatever the vectors' stride; J keeps its odd row stride
  * Ps, and every offset of sp_wave_layout is unchanged, so the engine's own first sweep works on the same state in LDS.
+ *
+ * Under a noise pattern (N = 2 ... FVB_MAX_PHIS precisions; include/fabber_device_spatial_wave_noise_model.h) the same two
+ * kernels in their CLASSES form: the layout is sp_wave_layout(P, N) with the same vectors behind it, 89.8 KB at P = 32,
+ * N = 8 of the 160 KB a workgroup may have (one workgroup per compute unit then).
  */
 #pragma once
 
@@ -28,9 +32,9 @@ namespace fvb
 // does not use otherwise: W = the vectors [2 P + 1][P] (wave_layout's pv; this layout's pv are 3 P per-parameter terms),
 // rden [P]. The engine works the launch's LDS bytes out with this function and the library's kernels place their arrays
 // with it: include/fabber_device_spatial_wave_model.h registers the double count at FVB_MAX_PARAMS as a probe.
-FVB_HD WaveLayout sp_wave_model_layout(int P)
+FVB_HD WaveLayout sp_wave_model_layout(int P, int N = 1)
 {
-    WaveLayout L = sp_wave_layout(P);
+    WaveLayout L = sp_wave_layout(P, N);
     int o = L.n_doubles;
     L.W = o;
     o += (2 * P + 1) * P;
@@ -51,9 +55,9 @@ struct SpwBodyRows
     __device__ __forceinline__ SpwBodyRows(const SpatialArgs &sa, int v, bool) : ma(wave_model_args<Eval>(sa.ka, v))
     {
     }
-    static __device__ __forceinline__ WaveLayout layout(int P)
+    static __device__ __forceinline__ WaveLayout layout(int P, int N = 1)
     {
-        return sp_wave_model_layout(P);
+        return sp_wave_model_layout(P, N);
     }
     // the 2 P + 1 model-space parameter vectors and rden (fwdmodel_linear.cc:157-161, fwdmodel.cc:375-379), as wave_recentre
     __device__ __forceinline__ void centre(const KernelArgs &ka, WaveCtx &cx) const
@@ -123,6 +127,19 @@ template <class Eval, bool NEEDF>
 __global__ __launch_bounds__(64) void vb_spatial_wave_noise_kernel(const SpatialArgs sa)
 {
     spw_noise<SpwBodyRows<Eval>, NEEDF>(sa);
+}
+
+// ... and for N = cfg.n_phis > 1 noise precisions
+template <class Eval>
+__global__ __launch_bounds__(64) void vb_spatial_wave_classes_setup_kernel(const SpatialArgs sa)
+{
+    spw_setup<SpwBodyRows<Eval>, true>(sa);
+}
+
+template <class Eval, bool NEEDF>
+__global__ __launch_bounds__(64) void vb_spatial_wave_classes_noise_kernel(const SpatialArgs sa)
+{
+    spw_noise<SpwBodyRows<Eval>, NEEDF, true>(sa);
 }
 
 #endif // __HIPCC__

@@ -25,6 +25,7 @@ _DEVICE_ENTRIES = (("device_model", vbabi.FvbDeviceModel, False),
                    ("device_spatial_model", vbabi.FvbDeviceSpatialModel, True),
                    ("device_spatial_noise_model", vbabi.FvbDeviceSpatialNoiseModel, True),
                    ("device_spatial_wave_model", vbabi.FvbDeviceSpatialWaveModel, False),
+                   ("device_spatial_wave_noise_model", vbabi.FvbDeviceSpatialWaveNoiseModel, False),
                    ("device_results_model", vbabi.FvbDeviceResultsModel, False),
                    ("device_init_model", vbabi.FvbDeviceInitModel, False))
 
@@ -104,6 +105,8 @@ def lib():
         L.fabber_vb_find_device_spatial_noise_model.argtypes = [C.c_char_p, C.c_int32, C.POINTER(vbabi.FvbDeviceSpatialNoiseModel)]
         L.fabber_vb_find_device_spatial_wave_model.restype = C.c_int32
         L.fabber_vb_find_device_spatial_wave_model.argtypes = [C.c_char_p, C.POINTER(vbabi.FvbDeviceSpatialWaveModel)]
+        L.fabber_vb_find_device_spatial_wave_noise_model.restype = C.c_int32
+        L.fabber_vb_find_device_spatial_wave_noise_model.argtypes = [C.c_char_p, C.POINTER(vbabi.FvbDeviceSpatialWaveNoiseModel)]
         L.fabber_nlls_kernel_name.restype = C.c_char_p
         L.fabber_nlls_kernel_name.argtypes = [cfgp]
         L.fabber_vb_spatial_kernel_name.restype = C.c_char_p
@@ -274,6 +277,26 @@ def find_device_spatial_wave_model(name):
     """a copy of the entry of `name` - the sizes and the LDS probe it reported, launcher - or None"""
     entry = vbabi.FvbDeviceSpatialWaveModel()
     return entry if lib().fabber_vb_find_device_spatial_wave_model(name.encode(), C.byref(entry)) else None
+
+
+def device_spatial_wave_noise_models():
+    """Names of the wave-per-voxel spatial-VB entries for noise patterns registered with the engine
+    (include/fabber_device_spatial_wave_noise_model.h): any parameter count up to FVB_MAX_PARAMS, 2 to FVB_MAX_PHIS precisions."""
+    return _listed("device_spatial_wave_noise_model", False)
+
+
+def register_device_spatial_wave_noise_model(descriptor):
+    _register("device_spatial_wave_noise_model", descriptor)
+
+
+def unregister_device_spatial_wave_noise_model(name):
+    _unregister("device_spatial_wave_noise_model", name)
+
+
+def find_device_spatial_wave_noise_model(name):
+    """a copy of the entry of `name` - the sizes and the LDS probe it reported, its families mask, launcher - or None"""
+    entry = vbabi.FvbDeviceSpatialWaveNoiseModel()
+    return entry if lib().fabber_vb_find_device_spatial_wave_noise_model(name.encode(), C.byref(entry)) else None
 
 
 def device_results_models():

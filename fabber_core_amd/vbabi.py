@@ -154,6 +154,17 @@ class FvbDeviceSpatialWaveModel(C.Structure):
                 ("lds_probe", C.c_uint32), ("launch", LAUNCH_FN)]
 
 
+SPATIAL_WAVE_NOISE_AR1, SPATIAL_WAVE_NOISE_PHIS = 1, 2  # FVB_SPATIAL_WAVE_NOISE_* (AR1: reserved, refused at registration)
+
+
+class FvbDeviceSpatialWaveNoiseModel(C.Structure):
+    """fvb_device_spatial_wave_noise_model: the wave-per-voxel spatial VB kernels of a device body under a noise pattern, any
+    parameter count (include/fabber_device_spatial_wave_noise_model.h); the launcher is FvbDeviceSpatialModel's"""
+    LAUNCH_FN = FvbDeviceSpatialModel.LAUNCH_FN
+    _fields_ = [("name", C.c_char_p), ("abi_version", C.c_int32), ("spatial_args_size", C.c_uint32), ("wave_layout_size", C.c_uint32),
+                ("lds_probe", C.c_uint32), ("families", C.c_int32), ("launch", LAUNCH_FN)]
+
+
 class FvbDeviceResultsModel(C.Structure):
     """fvb_device_results_model: the result-image kernel (model fit and residuals) of a device body, any parameter count
     (include/fabber_device_results_model.h)"""

@@ -816,8 +816,46 @@ const char *fabber_vb_device_spatial_wave_model_name(int32_t i); /* NULL when i 
 /* A copy of the entry of `name` in *entry and 1; 0 without one. */
 int32_t fabber_vb_find_device_spatial_wave_model(const char *name, fvb_device_spatial_wave_model *entry);
 
+/*
+ * The same family under a NOISE PATTERN of 2 to FVB_MAX_PHIS precisions (FABBER_DEVICE_SPATIAL_WAVE_NOISE_MODEL in
+ * include/fabber_device_spatial_wave_noise_model.h): a registry of its own keyed by the name alone, independent of the one
+ * above (an entry needs a body of its name, not the white-noise wave entry). `families` says which noise policies the
+ * library compiled the set-up kernel and the second sweep around: FVB_SPATIAL_WAVE_NOISE_PHIS = white noise with 2 to
+ * FVB_MAX_PHIS precisions; FVB_SPATIAL_WAVE_NOISE_AR1 is reserved and refused at registration. With an entry next to a
+ * body of the same name, a configuration with FVB_MODEL_PLUGIN, white noise and n_phis = N > 1 takes these kernels for 1 to
+ * FVB_MAX_PARAMS parameters wherever the registry of fabber_vb_register_device_spatial_noise_model has no PHIS entry for
+ * (name, n_params) that covers N: the kernel table's name is spatial<NAME,wave,phisN>. AR(1) noise keeps -40. The state
+ * image has the class statistics behind the rows of the one-precision image (5 724 rows at 32 parameters and 8
+ * precisions: 46 KB per voxel); a run whose image the device cannot hold is refused with -40 and the figure. `launch` is
+ * the launcher type of the registry above; it answers -40 for fewer LDS bytes than its own layout for (n_params, n_phis)
+ * needs. lds_probe is the number of doubles of the family's LDS layout at FVB_MAX_PARAMS parameters and FVB_MAX_PHIS
+ * precisions (fvb::sp_wave_model_layout).
+ * Registration is refused with -24 (descriptor, name or launcher NULL, name too long, a mask that is empty or names a
+ * family this engine does not know), -25 (another ABI version), -26 (another sizeof(fvb::SpatialArgs) or
+ * sizeof(fvb::WaveLayout), another LDS layout) or -27 (duplicate name); unregistering a name that is not registered
+ * answers -28. The lifetime rules are those of fabber_vb_register_device_model.
+ */
+#define FVB_SPATIAL_WAVE_NOISE_AR1 1  /* reserved */
+#define FVB_SPATIAL_WAVE_NOISE_PHIS 2
+typedef struct fvb_device_spatial_wave_noise_model
+{
+    const char *name;
+    int32_t abi_version;        /* FVB_ABI_VERSION the library was compiled against */
+    uint32_t spatial_args_size; /* sizeof(fvb::SpatialArgs) */
+    uint32_t wave_layout_size;  /* sizeof(fvb::WaveLayout) */
+    uint32_t lds_probe;         /* fvb::sp_wave_model_layout(FVB_MAX_PARAMS, FVB_MAX_PHIS).n_doubles */
+    int32_t families;           /* FVB_SPATIAL_WAVE_NOISE_PHIS: not empty */
+    fvb_device_spatial_launch_fn launch;
+} fvb_device_spatial_wave_noise_model;
+int32_t fabber_vb_register_device_spatial_wave_noise_model(const fvb_device_spatial_wave_noise_model *model);
+int32_t fabber_vb_unregister_device_spatial_wave_noise_model(const char *name);
+int32_t fabber_vb_device_spatial_wave_noise_model_count(void);
+const char *fabber_vb_device_spatial_wave_noise_model_name(int32_t i); /* NULL when i is out of range */
+/* A copy of the entry of `name` in *entry and 1; 0 without one. */
+int32_t fabber_vb_find_device_spatial_wave_noise_model(const char *name, fvb_device_spatial_wave_noise_model *entry);
+
 /* Which kernel table fabber_vb_run_spatial_* would take for a configuration: "spatial<exp,2>" / "spatial<NAME,P>" /
- * "spatial<NAME,P,ar1>" / "spatial<NAME,wave>" ..., "" where the run would answer -40 or -44 (no kernels for the model /
+ * "spatial<NAME,P,ar1>" / "spatial<NAME,wave>" / "spatial<NAME,wave,phis2>" ..., "" where the run would answer -40 or -44 (no kernels for the model /
  * parameter count / noise model; a library body without a spatial entry for the noise model). Reads n_params, n_phis,
  * noise, ar_cross_terms, need_f, model and device_model. */
 const char *fabber_vb_spatial_kernel_name(const fvb_config *cfg);

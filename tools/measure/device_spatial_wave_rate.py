@@ -19,6 +19,13 @@ overhead included). The host family's second sweep cannot be started alone - it 
 upload of the linearisation and the next download - so for the host route the tool gives the whole iteration only.
 
     python tools/measure/device_spatial_wave_rate.py [--models multiexp_spw,linear_spw] [--size 64] [--json PATH]
+
+--patterns: instead of the above, the sweeps one by one under a noise pattern (the kernels of
+include/fabber_device_spatial_wave_noise_model.h, tests/plugins/fwdmodel_spatial_wave_noise_models.hip): linear_spwn with 10 and
+with 32 cosine regressors under 2 and under 8 precisions (spatial<linear_spwn,wave,phisN>) next to linear_spw of the same shape
+under white noise with one precision (spatial<linear_spw,wave>), and two exponentials (4 parameters) under pattern 12 on the
+wave kernels (multiexp_spwn), on the lane kernels (multiexp_spwn_both: spatial<multiexp_spwn_both,4,pattern2>, per-level first
+sweep as the others) and under one precision (multiexp_spw) - same process, same job.
 """
 import argparse
 import json
@@ -34,6 +41,7 @@ import numpy as np
 import torch
 
 import device_spatial_wave_lib
+import device_spatial_wave_noise_lib
 from fabber_core_amd import fabber, hiplib, vbabi
 from fabber_core_amd.device import DeviceProblem
 from fabber_core_amd.spatial_mgpu import _Run
@@ -44,11 +52,13 @@ ap.add_argument("--size", type=int, default=64)
 ap.add_argument("--times", type=int, default=100)
 ap.add_argument("--json", default=None)
 ap.add_argument("--skip-host-route", action="store_true")
+ap.add_argument("--patterns", action="store_true")
+ap.add_argument("--iters", type=int, default=10)
 args = ap.parse_args()
 
 library = device_spatial_wave_lib.build_spatial_wave_library()
 hiplib.load_model_library(library)
-SHAPE, T, ITERS, SHORT = (args.size,) * 3, args.times, 10, 2
+SHAPE, T, ITERS, SHORT = (args.size,) * 3, args.times, args.iters, 2
 coords = vbabi.grid_coords(SHAPE)
 V = coords.shape[1]
 sp = vbabi.SpatialHolder(coords)
@@ -91,9 +101,10 @@ def linear():
     return y, holder, {"model": "linear_spw", "basis": basis, "param-spatial-priors": "M" + "N" * (P - 1)}, "Parameter_1"
 
 
-def sweeps_one_by_one(name, holder, y):
+def sweeps_one_by_one(name, holder, y, kernels=None):
     """the device route's a_K update, first sweep and second sweep per iteration, the stream drained after each"""
-    assert hiplib.spatial_kernel_name(holder) == "spatial<%s,wave>" % name
+    kernels = kernels or "spatial<%s,wave>" % name
+    assert hiplib.spatial_kernel_name(holder) == kernels, (hiplib.spatial_kernel_name(holder), kernels)
     prob = DeviceProblem(holder, y, "cuda:0")
     prob.run_spatial(sp)  # warm-up: code objects, memory pool
     assert np.count_nonzero(prob.results()["status"]) < max(1, V // 1000)
@@ -115,12 +126,14 @@ def sweeps_one_by_one(name, holder, y):
                 ms[what].append((time.perf_counter() - t0) * 1e3)
     finally:
         run.close()
-    out = dict(what="sweeps", route="spatial<%s,wave>" % name, voxels=V, timepoints=T, parameters=holder.cfg.n_params, ms_open_with_set_up=ms_open,
+    out = dict(what="sweeps", route=kernels, voxels=V, timepoints=T, parameters=holder.cfg.n_params, ms_open_with_set_up=ms_open,
                **{"ms_%s_median" % k: float(np.median(v[1:])) for k, v in ms.items()}, **{"ms_%s_all" % k: v for k, v in ms.items()})
     results.append(out)
     print("sweeps  %-28s %7d voxels T=%d P=%d: open + set-up %.1f ms; per iteration (median of iterations 2..%d) a_K %.2f ms, first sweep %.2f ms, "
           "second sweep %.2f ms" % (out["route"], V, T, holder.cfg.n_params, ms_open, ITERS, out["ms_ak_median"], out["ms_first_median"],
                                     out["ms_second_median"]), flush=True)
+    out["ms_iteration_median"] = float(np.median(np.array(ms["ak"][1:]) + np.array(ms["first"][1:]) + np.array(ms["second"][1:])))
+    print("sweeps  %-28s per spatial iteration %.2f ms" % (out["route"], out["ms_iteration_median"]), flush=True)
     del prob
 
 
@@ -155,6 +168,55 @@ def whole_calls(name, y, model_opts, first):
         print("ratios  %-28s host route / device route: whole call of %d iterations %.2f, per iteration %.2f"
               % (name, ITERS, ratio["whole_call_host_over_device"], ratio["per_iteration_host_over_device"]), flush=True)
 
+
+def linear_pattern(P, pattern):
+    """P cosine regressors, a prior M on the first; pattern None: linear_spw under one precision, else linear_spwn"""
+    X = np.cos(np.pi * np.arange(P)[None, :] * (np.arange(T)[:, None] + 0.5) / T)
+    theta = np.stack([scale / (k + 1) for k in range(P)])
+    y = (X @ theta + np.random.default_rng(P).normal(0, 0.1, (T, V))).astype(np.float32)
+    kw = dict(param_overrides={"Parameter_1": dict(type="M")}, **({"noise_pattern": pattern} if pattern else {}))
+    init = hiplib.initial_mvn(vbabi.build_config(vbabi.MODEL_LINEAR, V, T, design=X, **kw), y)
+    n = P + (len(set(pattern)) if pattern else 1)
+    for k in range(P):
+        init[n * (n + 1) // 2 + k] = 1.0 / (k + 1)
+    name = "linear_spwn" if pattern else "linear_spw"
+    return name, y, vbabi.build_config(vbabi.MODEL_PLUGIN, V, T, device_model=name, constants=X, init_mvn=init, max_iterations=ITERS,
+                                       params=vbabi.model_parameter_defaults(vbabi.MODEL_LINEAR, n_basis=P), **kw)
+
+
+def biexp_pattern(name, pattern):
+    num, dt = 2, 0.006
+    rates, amps = np.array([0.5, 12.0]), np.array([1.0, 0.6])
+    t = np.arange(T) * dt
+    y = (sum(amps[i] * scale[None, :] * np.exp(-rates[i] * t)[:, None] for i in range(num))
+         + np.random.default_rng(4).normal(0, 0.02, (T, V))).astype(np.float32)
+    kw = dict(num_exps=num, dt=dt, param_overrides={"amp1": dict(type="M")}, **({"noise_pattern": pattern} if pattern else {}))
+    init = hiplib.initial_mvn(vbabi.build_config(vbabi.MODEL_EXP, V, T, **kw), y)
+    n = 2 * num + (len(set(pattern)) if pattern else 1)
+    for i in range(num):
+        init[n * (n + 1) // 2 + 2 * i], init[n * (n + 1) // 2 + 2 * i + 1] = np.log(amps[i]), np.log(rates[i])
+    return y, vbabi.build_config(vbabi.MODEL_PLUGIN, V, T, device_model=name, init_mvn=init, max_iterations=ITERS,
+                                 params=vbabi.model_parameter_defaults(vbabi.MODEL_EXP, num_exps=num), **kw)
+
+
+if args.patterns:
+    hiplib.load_model_library(device_spatial_wave_noise_lib.build_spatial_wave_noise_library())
+    os.environ["FVB_SPATIAL_PER_LEVEL"] = "1"  # (the lane route's first sweep as the wave routes': one launch per level)
+    for P in (10, 32):
+        for pattern in (None, "12", "12345678"):
+            name, y, holder = linear_pattern(P, pattern)
+            sweeps_one_by_one(name, holder, y, None if pattern is None else "spatial<%s,wave,phis%d>" % (name, len(pattern)))
+            if args.json:
+                with open(args.json, "w") as fh:
+                    json.dump(results, fh, indent=1)
+    for name, pattern, kernels in (("multiexp_spw", None, None), ("multiexp_spwn", "12", "spatial<multiexp_spwn,wave,phis2>"),
+                                   ("multiexp_spwn_both", "12", "spatial<multiexp_spwn_both,4,pattern2>")):
+        y, holder = biexp_pattern(name, pattern)
+        sweeps_one_by_one(name, holder, y, kernels)
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(results, fh, indent=1)
+    sys.exit(0)
 
 for name in args.models.split(","):
     y, holder, model_opts, first = {"multiexp_spw": multiexp, "linear_spw": linear}[name]()
