@@ -32,7 +32,17 @@ struct DeviceStructSize
 //   bad_params(m) why m's parameter count has no kernels (NULL: it has)
 //   entry(name, n_params), is   how the messages call one entry, with its verb ("is" / "are")
 //   absent(name, n_params)      what unregistering an entry that is not there is told
+//   absent_code   (optional) the code for "not registered" where first_code - 4 is taken by something else
 template <class D> struct DeviceRegistryTraits;
+
+template <class Tr> constexpr auto device_registry_absent_code(int) -> decltype(Tr::absent_code)
+{
+    return Tr::absent_code;
+}
+template <class Tr> constexpr int device_registry_absent_code(long)
+{
+    return Tr::first_code - 4;
+}
 
 // The key of an entry is (name, parameter count); the descriptors of the wave body, of the result-image kernel and of
 // the initial-posterior kernel have no count, nor have the wave-per-voxel spatial kernels (a runtime value there): 0
@@ -45,6 +55,10 @@ inline int registered_params(const fvb_device_spatial_wave_model &)
     return 0;
 }
 inline int registered_params(const fvb_device_spatial_wave_noise_model &)
+{
+    return 0;
+}
+inline int registered_params(const fvb_device_spatial_wave_ar_model &)
 {
     return 0;
 }
@@ -113,7 +127,7 @@ public:
         std::lock_guard<std::mutex> hold(lock_);
         const size_t i = at(name, n_params);
         if (i == models_.size())
-            return api_fail(Tr::first_code - 4, Tr::absent(name, n_params));
+            return api_fail(device_registry_absent_code<Tr>(0), Tr::absent(name, n_params));
         models_.erase(models_.begin() + (long)i);
         return 0;
     }

@@ -143,6 +143,32 @@ template <> struct DeviceRegistryTraits<fvb_device_spatial_wave_noise_model>
         return "no " + entry(name, 0) + " are registered";
     }
 };
+// ... and the family's kernels under AR(1) noise with one echo (include/fabber_device_spatial_wave_ar_model.h), by name:
+// a registry of its own (the reserved AR1 bit of the pattern registry above stays refused)
+SpatialKernels get_spatial_kernels_wave_ar_model(int P, bool need_f);
+uint32_t spatial_wave_ar_model_lds_probe();
+template <> struct DeviceRegistryTraits<fvb_device_spatial_wave_ar_model>
+{
+    static constexpr const char *noun = "device spatial wave AR(1) model", *is = "are";
+    static constexpr int first_code = -86, absent_code = -96; // (-90 is another registry's)
+    static std::vector<DeviceStructSize> sizes(const fvb_device_spatial_wave_ar_model &m)
+    {
+        return { { "SpatialArgs", m.spatial_args_size, sizeof(SpatialArgs) }, { "WaveLayout", m.wave_layout_size, spatial_wave_layout_size() },
+            { "LDS doubles under AR(1) noise at FVB_MAX_PARAMS parameters", m.lds_probe, spatial_wave_ar_model_lds_probe() } };
+    }
+    static const char *bad_params(const fvb_device_spatial_wave_ar_model &)
+    {
+        return nullptr;
+    }
+    static std::string entry(const std::string &name, int)
+    {
+        return "wave-per-voxel AR(1) spatial kernels of a device model named '" + name + "'";
+    }
+    static std::string absent(const std::string &name, int)
+    {
+        return "no " + entry(name, 0) + " are registered";
+    }
+};
 } // namespace fvb
 namespace
 {
@@ -169,7 +195,8 @@ thread_local std::string g_spatial_kernel_name;
 // policy's table and the launcher of the library's entry for these policies (spatial_route_library_noise). Without a lane
 // entry for (name, P) under white noise with one precision: the wave-per-voxel family around the body, where the library
 // registered it (spatial_route_library_wave); without a lane entry that covers (name, P) under a noise pattern of 2 to 8
-// precisions: the same family in its form for several precisions (spatial_route_library_wave_noise). Nothing (-40) without an entry that covers the parameter count and the noise
+// precisions: the same family in its form for several precisions (spatial_route_library_wave_noise); without a lane entry
+// for (name, P) under AR(1) noise with one echo: the family's AR(1) form (spatial_route_library_wave_ar). Nothing (-40) without an entry that covers the parameter count and the noise
 // model, under the other noise models, or for a name without a wave body (which the argument checks answer with -16
 // before this is asked).
 static SpatialRoute spatial_route_library_noise(const fvb_config *cfg, int kind, const std::string &name)
@@ -233,6 +260,25 @@ static SpatialRoute spatial_route_library_wave_noise(const fvb_config *cfg, int 
     route.library = entry.launch;
     return route;
 }
+// AR(1) noise with one echo and no lane entry for (name, P) with the AR1 family: the wave-per-voxel family in its AR(1) form
+// where the library compiled it (include/fabber_device_spatial_wave_ar_model.h). The engine's a_K kernels and pack kernel,
+// its first sweep (with the AR free energy where F is evaluated), the state image with the rows of SpAr1, the LDS of the
+// layout with the AR areas.
+static SpatialRoute spatial_route_library_wave_ar(const fvb_config *cfg, int kind, const std::string &name)
+{
+    SpatialRoute route;
+    fvb_device_spatial_wave_ar_model entry;
+    if (kind != FVB_SPNZ_AR1 || cfg->n_params < 1 || cfg->n_params > FVB_MAX_PARAMS
+        || !DeviceRegistry<fvb_device_spatial_wave_ar_model>::instance().find(name, 0, &entry))
+        return route;
+    const SpatialKernels k = get_spatial_kernels_wave_ar_model(cfg->n_params, cfg->need_f != 0);
+    if (!k.theta || !k.wave)
+        return route;
+    route.name = "spatial<" + name + ",wave,ar1>";
+    route.k = k;
+    route.library = entry.launch;
+    return route;
+}
 static SpatialRoute spatial_route_library(const fvb_config *cfg, int kind)
 {
     SpatialRoute route;
@@ -243,7 +289,9 @@ static SpatialRoute spatial_route_library(const fvb_config *cfg, int kind)
     if (kind != FVB_SPNZ_WHITE)
     {
         route = spatial_route_library_noise(cfg, kind, name);
-        return route.found() ? route : spatial_route_library_wave_noise(cfg, kind, name);
+        if (route.found())
+            return route;
+        return kind == FVB_SPNZ_AR1 ? spatial_route_library_wave_ar(cfg, kind, name) : spatial_route_library_wave_noise(cfg, kind, name);
     }
     if (!DeviceRegistry<fvb_device_spatial_model>::instance().find(name, cfg->n_params, &entry))
         return spatial_route_library_wave(cfg, name);
@@ -393,10 +441,12 @@ int fvb_spatial_run::open(const fvb_config *cfg_, const fvb_spatial *sp_, const 
 // launched with; upload_plan() adds the rest.
 int fvb_spatial_run::start_setup(const void *d_data, const fvb_outputs *d_out)
 {
-    if (k.wave && cfg.n_phis > 1)
+    const bool wave_ar = k.wave && cfg.noise == FVB_NOISE_AR1;
+    if (k.wave && (cfg.n_phis > 1 || wave_ar))
     {
-        // the state image with every class's statistics (46 KB per voxel at 32 parameters and 8 precisions): worked out
-        // before the run, a device that cannot hold it says so instead of failing inside the allocation
+        // the state image with every class's statistics (46 KB per voxel at 32 parameters and 8 precisions) or with the
+        // AR(1) moments (19 KB per voxel at 32 parameters): worked out before the run, a device that cannot hold it says
+        // so instead of failing inside the allocation
         const size_t bytes = sizeof(double) * (size_t)k.state_rows * (size_t)V;
         size_t free_bytes = 0, total_bytes = 0;
         FVB_HIP_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
@@ -408,8 +458,8 @@ int fvb_spatial_run::start_setup(const void *d_data, const fvb_outputs *d_out)
                 free_bytes += (size_t)(reserved - used);
         (void)hipGetLastError();
         if (bytes > free_bytes)
-            return api_fail(-40, "spatial VB with " + std::to_string(P) + " parameters and " + std::to_string(cfg.n_phis)
-                    + " noise precisions keeps " + std::to_string(k.state_rows) + " rows per voxel: " + std::to_string(bytes >> 20) + " MiB for "
+            return api_fail(-40, "spatial VB with " + std::to_string(P) + " parameters and "
+                    + (wave_ar ? std::string("AR(1) noise") : std::to_string(cfg.n_phis) + " noise precisions") + " keeps " + std::to_string(k.state_rows) + " rows per voxel: " + std::to_string(bytes >> 20) + " MiB for "
                     + std::to_string(V) + " voxels, the device has " + std::to_string(free_bytes >> 20) + " MiB free");
         if (k.wave_lds > 64 * 1024) // (more dynamic LDS than a kernel gets without asking; the library's launcher asks for its own)
             FVB_HIP_CHECK(hipFuncSetAttribute((const void *)k.theta, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.wave_lds));
@@ -1150,6 +1200,31 @@ const char *fabber_vb_device_spatial_wave_model_name(int32_t i)
 int32_t fabber_vb_find_device_spatial_wave_model(const char *name, fvb_device_spatial_wave_model *entry)
 {
     return (name && entry && DeviceRegistry<fvb_device_spatial_wave_model>::instance().find(name, 0, entry)) ? 1 : 0;
+}
+
+int32_t fabber_vb_register_device_spatial_wave_ar_model(const fvb_device_spatial_wave_ar_model *model)
+{
+    return DeviceRegistry<fvb_device_spatial_wave_ar_model>::instance().add(model);
+}
+
+int32_t fabber_vb_unregister_device_spatial_wave_ar_model(const char *name)
+{
+    return DeviceRegistry<fvb_device_spatial_wave_ar_model>::instance().remove(name, 0);
+}
+
+int32_t fabber_vb_device_spatial_wave_ar_model_count(void)
+{
+    return DeviceRegistry<fvb_device_spatial_wave_ar_model>::instance().count();
+}
+
+const char *fabber_vb_device_spatial_wave_ar_model_name(int32_t i)
+{
+    return DeviceRegistry<fvb_device_spatial_wave_ar_model>::instance().name(i);
+}
+
+int32_t fabber_vb_find_device_spatial_wave_ar_model(const char *name, fvb_device_spatial_wave_ar_model *entry)
+{
+    return (name && entry && DeviceRegistry<fvb_device_spatial_wave_ar_model>::instance().find(name, 0, entry)) ? 1 : 0;
 }
 
 int32_t fabber_vb_register_device_spatial_wave_noise_model(const fvb_device_spatial_wave_noise_model *model)

@@ -84,6 +84,41 @@ FVB_HD int sp_wide_state_rows(int P, int N)
     return N > 1 ? sp_wide_class_rows(P, N).ROWS : sp_wide_layout(P).ROWS;
 }
 
+// Under AR(1) noise with one echo and no cross terms (vb_spatial_wave_ar.h) the rows of SpAr1<P> (vb_spatial_noise.h)
+// follow the rows above, in that policy's order: the alpha posterior (means, c11, c12, c22, a1, a2), the diagonal and
+// lag-1 moments Ad, C, ud, uc, sd, sc and the first and last rows J1, JT, r1, rT. The rows A, U, S above hold the EFFECTIVE
+// moments J'QJ, J'Q(y - g), (y - g)'Q(y - g) then and B, C phi's posterior: the first sweep without F and the a_K
+// kernels work on this image as on the one-precision image.
+struct SpWideArRows
+{
+    int AL, AD, CC, UD, UC, SD, SC, J1, JT, R1, RT, ROWS;
+};
+
+FVB_HD SpWideArRows sp_wide_ar_rows(int P)
+{
+    const SpWideLayout S = sp_wide_layout(P);
+    SpWideArRows R;
+    R.AL = S.ROWS;
+    R.AD = R.AL + 7;
+    R.CC = R.AD + S.PT;
+    R.UD = R.CC + S.PT;
+    R.UC = R.UD + P;
+    R.SD = R.UC + P;
+    R.SC = R.SD + 1;
+    R.J1 = R.SC + 1;
+    R.JT = R.J1 + P;
+    R.R1 = R.JT + P;
+    R.RT = R.R1 + 1;
+    R.ROWS = R.RT + 1;
+    return R;
+}
+
+// rows of the state image under AR(1) noise: 2 415 at P = 32 (19 KB per voxel)
+FVB_HD int sp_wide_ar_state_rows(int P)
+{
+    return sp_wide_ar_rows(P).ROWS;
+}
+
 // timepoints of J staged in LDS at a time (one per lane where a pass works on timepoints)
 constexpr int SPW_TC = 64;
 // N > 1: the chunk's unmasked timepoints listed class by class (spw_class_lists), SPW_TC + 16 int32
@@ -1164,8 +1199,10 @@ __global__ __launch_bounds__(256) void vb_spatial_wide_pack_kernel(const Spatial
     const int P = ka.cfg.n_params;
     const SpWideLayout S = sp_wide_layout(P);
     const size_t V = (size_t)ka.cfg.n_voxels;
-    // (N > 1 precisions in this family: white noise under a pattern, the class rows of the state image)
-    const int N = (ka.cfg.noise == FVB_NOISE_WHITE && ka.cfg.n_phis > 1) ? ka.cfg.n_phis : 1;
+    // (N > 1 precisions in this family: white noise under a pattern, the class rows of the state image; AR(1) noise:
+    // alpha_1, alpha_2 and phi)
+    const bool ar = ka.cfg.noise == FVB_NOISE_AR1;
+    const int N = ar ? 3 : ((ka.cfg.noise == FVB_NOISE_WHITE && ka.cfg.n_phis > 1) ? ka.cfg.n_phis : 1);
     const int n = P + N, nCov = n * (n + 1) / 2;
     const double *p = sa.state + v;
     double *dst = ka.out.mvn + v;
@@ -1173,7 +1210,22 @@ __global__ __launch_bounds__(256) void vb_spatial_wide_pack_kernel(const Spatial
         dst[(size_t)i * V] = p[(size_t)(S.SIG + i) * V];
     for (int i = 0; i < P; i++)
         dst[(size_t)(nCov + i) * V] = p[(size_t)(S.M + i) * V];
-    if (N > 1) // noisemodel_white.cc:55-68, in the order of SpPattern's pack_noise
+    if (ar) // Ar1cParams::OutputAsMVN (noisemodel_ar.cc:287-300), as SpAr1's pack_noise
+    {
+        const double *al = p + (size_t)sp_wide_ar_rows(P).AL * V;
+        const double b = p[(size_t)S.B * V], c = p[(size_t)S.C * V];
+        for (int r = P; r < n; r++)
+            for (int cc = 0; cc <= r; cc++)
+                dst[(size_t)tri(r, cc) * V] = 0.0;
+        dst[(size_t)tri(P, P) * V] = al[2 * V];
+        dst[(size_t)tri(P + 1, P) * V] = al[3 * V];
+        dst[(size_t)tri(P + 1, P + 1) * V] = al[4 * V];
+        dst[(size_t)tri(P + 2, P + 2) * V] = b * b * c;
+        dst[(size_t)(nCov + P) * V] = al[0];
+        dst[(size_t)(nCov + P + 1) * V] = al[V];
+        dst[(size_t)(nCov + P + 2) * V] = b * c;
+    }
+    else if (N > 1) // noisemodel_white.cc:55-68, in the order of SpPattern's pack_noise
     {
         const SpWideClassRows R = sp_wide_class_rows(P, N);
         for (int k = 0; k < N; k++)

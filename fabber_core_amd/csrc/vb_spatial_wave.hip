@@ -1,6 +1,6 @@
 // Spatial-VB kernels of the wave-per-voxel family (vb_spatial_wave.h): host-evaluated models, runtime parameter count
 #define FVB_SPATIAL_WAVE_ENGINE 1 // (the family's kernels that are no templates are defined here, once)
-#include "vb_spatial_wave_model.h"
+#include "vb_spatial_wave_ar.h"
 
 namespace fvb
 {
@@ -54,6 +54,24 @@ SpatialKernels get_spatial_kernels_wave_noise_model(int P, int N, bool need_f)
 uint32_t spatial_wave_noise_model_lds_probe()
 {
     return (uint32_t)sp_wave_model_layout(FVB_MAX_PARAMS, FVB_MAX_PHIS).n_doubles;
+}
+// ... and under AR(1) noise with one echo and no cross terms (include/fabber_device_spatial_wave_ar_model.h): the first
+// sweep with the AR free energy where F is evaluated (without F it is the one-precision kernel, on the effective moments),
+// the state image with the rows of SpAr1, the LDS of the layout with the AR areas
+SpatialKernels get_spatial_kernels_wave_ar_model(int P, bool need_f)
+{
+    SpatialKernels k = get_spatial_kernels_wave_model(P, need_f);
+    if (!k.theta)
+        return SpatialKernels{};
+    if (need_f)
+        k.theta = vb_spatial_wave_ar_theta_kernel;
+    k.state_rows = sp_wide_ar_state_rows(P);
+    k.wave_lds = sp_wave_ar_model_layout(P).bytes;
+    return k;
+}
+uint32_t spatial_wave_ar_model_lds_probe()
+{
+    return (uint32_t)sp_wave_ar_model_layout(FVB_MAX_PARAMS).n_doubles;
 }
 // what a library's entry must report as its lds_probe and as its wave_layout_size
 uint32_t spatial_wave_model_lds_probe()

@@ -26,6 +26,7 @@ _DEVICE_ENTRIES = (("device_model", vbabi.FvbDeviceModel, False),
                    ("device_spatial_noise_model", vbabi.FvbDeviceSpatialNoiseModel, True),
                    ("device_spatial_wave_model", vbabi.FvbDeviceSpatialWaveModel, False),
                    ("device_spatial_wave_noise_model", vbabi.FvbDeviceSpatialWaveNoiseModel, False),
+                   ("device_spatial_wave_ar_model", vbabi.FvbDeviceSpatialWaveArModel, False),
                    ("device_results_model", vbabi.FvbDeviceResultsModel, False),
                    ("device_init_model", vbabi.FvbDeviceInitModel, False))
 
@@ -107,6 +108,8 @@ def lib():
         L.fabber_vb_find_device_spatial_wave_model.argtypes = [C.c_char_p, C.POINTER(vbabi.FvbDeviceSpatialWaveModel)]
         L.fabber_vb_find_device_spatial_wave_noise_model.restype = C.c_int32
         L.fabber_vb_find_device_spatial_wave_noise_model.argtypes = [C.c_char_p, C.POINTER(vbabi.FvbDeviceSpatialWaveNoiseModel)]
+        L.fabber_vb_find_device_spatial_wave_ar_model.restype = C.c_int32
+        L.fabber_vb_find_device_spatial_wave_ar_model.argtypes = [C.c_char_p, C.POINTER(vbabi.FvbDeviceSpatialWaveArModel)]
         L.fabber_nlls_kernel_name.restype = C.c_char_p
         L.fabber_nlls_kernel_name.argtypes = [cfgp]
         L.fabber_vb_spatial_kernel_name.restype = C.c_char_p
@@ -297,6 +300,26 @@ def find_device_spatial_wave_noise_model(name):
     """a copy of the entry of `name` - the sizes and the LDS probe it reported, its families mask, launcher - or None"""
     entry = vbabi.FvbDeviceSpatialWaveNoiseModel()
     return entry if lib().fabber_vb_find_device_spatial_wave_noise_model(name.encode(), C.byref(entry)) else None
+
+
+def device_spatial_wave_ar_models():
+    """Names of the wave-per-voxel spatial-VB entries for AR(1) noise registered with the engine
+    (include/fabber_device_spatial_wave_ar_model.h): any parameter count up to FVB_MAX_PARAMS, one echo, no cross terms."""
+    return _listed("device_spatial_wave_ar_model", False)
+
+
+def register_device_spatial_wave_ar_model(descriptor):
+    _register("device_spatial_wave_ar_model", descriptor)
+
+
+def unregister_device_spatial_wave_ar_model(name):
+    _unregister("device_spatial_wave_ar_model", name)
+
+
+def find_device_spatial_wave_ar_model(name):
+    """a copy of the entry of `name` - the sizes and the LDS probe it reported, its launcher - or None"""
+    entry = vbabi.FvbDeviceSpatialWaveArModel()
+    return entry if lib().fabber_vb_find_device_spatial_wave_ar_model(name.encode(), C.byref(entry)) else None
 
 
 def device_results_models():

@@ -165,6 +165,14 @@ class FvbDeviceSpatialWaveNoiseModel(C.Structure):
                 ("lds_probe", C.c_uint32), ("families", C.c_int32), ("launch", LAUNCH_FN)]
 
 
+class FvbDeviceSpatialWaveArModel(C.Structure):
+    """fvb_device_spatial_wave_ar_model: the wave-per-voxel spatial VB kernels of a device body under AR(1) noise, any
+    parameter count (include/fabber_device_spatial_wave_ar_model.h); the launcher is FvbDeviceSpatialModel's"""
+    LAUNCH_FN = FvbDeviceSpatialModel.LAUNCH_FN
+    _fields_ = [("name", C.c_char_p), ("abi_version", C.c_int32), ("spatial_args_size", C.c_uint32), ("wave_layout_size", C.c_uint32),
+                ("lds_probe", C.c_uint32), ("launch", LAUNCH_FN)]
+
+
 class FvbDeviceResultsModel(C.Structure):
     """fvb_device_results_model: the result-image kernel (model fit and residuals) of a device body, any parameter count
     (include/fabber_device_results_model.h)"""

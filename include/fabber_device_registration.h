@@ -1,7 +1,7 @@
 /*
  * fabber_device_registration.h - what the headers that compile the engine's kernels around a model library's device
  * body share (fabber_device_model.h, fabber_device_lane_model.h, fabber_device_lane_noise_model.h, fabber_device_nlls_model.h,
- * fabber_device_spatial_model.h, fabber_device_spatial_noise_model.h, fabber_device_spatial_wave_model.h, fabber_device_spatial_wave_noise_model.h, fabber_device_results_model.h, fabber_device_init_model.h): the static object that registers an entry with the engine, the token pasting of
+ * fabber_device_spatial_model.h, fabber_device_spatial_noise_model.h, fabber_device_spatial_wave_model.h, fabber_device_spatial_wave_noise_model.h, fabber_device_spatial_wave_ar_model.h, fabber_device_results_model.h, fabber_device_init_model.h): the static object that registers an entry with the engine, the token pasting of
  * their macros and the way a launcher hands its error text back. A library includes those headers, not this one.
  */
 #ifndef FABBER_DEVICE_REGISTRATION_H

@@ -21,8 +21,9 @@
  *
  * The engine takes these kernels under white noise with one precision. Noise patterns of 2 to 8 precisions have a line of
  * their own (fabber_device_spatial_wave_noise_model.h: the same two kernels in their form for several precisions; a name
- * with this line alone keeps -40 under a pattern). AR(1) noise, a volume cut into z-slabs over several devices and more
- * than FVB_MAX_PARAMS parameters keep the host route (-40 from the engine, after which method=spatialvb evaluates the
+ * with this line alone keeps -40 under a pattern), and so has AR(1) noise with one echo and no cross terms
+ * (fabber_device_spatial_wave_ar_model.h). AR(1) noise with two echoes or cross terms, a volume cut into z-slabs over
+ * several devices and more than FVB_MAX_PARAMS parameters keep the host route (-40 from the engine, after which method=spatialvb evaluates the
  * model's host code as before). The initial posterior is an image (init_mvn): from
  * the library's kernel for it where the library uses the macro of fabber_device_init_model.h, else from the model's host
  * code.

@@ -17,7 +17,8 @@
  * fabber_device_spatial_wave_model.h is NOT required (a name without it keeps -40 under white noise with one precision).
  * FAMILIES is a compile-time mask of the noise policies the kernels are compiled for, as in
  * fabber_device_spatial_noise_model.h: FVB_SPATIAL_WAVE_NOISE_PHIS = white noise with 2 to FVB_MAX_PHIS precisions.
- * FVB_SPATIAL_WAVE_NOISE_AR1 is reserved: AR(1) noise has no kernels in this family and the engine refuses a mask with it.
+ * FVB_SPATIAL_WAVE_NOISE_AR1 is reserved and the engine refuses a mask with it: the family's kernels under AR(1) noise have
+ * a header and a registry of their own (fabber_device_spatial_wave_ar_model.h).
  *
  * A name may have lines of fabber_device_spatial_noise_model.h as well: for a parameter count with such a line and 2 to 4
  * precisions the engine takes the lane kernels (spatial<NAME,P,pattern2>), for every other count and for 5 to 8

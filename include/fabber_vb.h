@@ -824,7 +824,7 @@ int32_t fabber_vb_find_device_spatial_wave_model(const char *name, fvb_device_sp
  * FVB_MAX_PHIS precisions; FVB_SPATIAL_WAVE_NOISE_AR1 is reserved and refused at registration. With an entry next to a
  * body of the same name, a configuration with FVB_MODEL_PLUGIN, white noise and n_phis = N > 1 takes these kernels for 1 to
  * FVB_MAX_PARAMS parameters wherever the registry of fabber_vb_register_device_spatial_noise_model has no PHIS entry for
- * (name, n_params) that covers N: the kernel table's name is spatial<NAME,wave,phisN>. AR(1) noise keeps -40. The state
+ * (name, n_params) that covers N: the kernel table's name is spatial<NAME,wave,phisN>. AR(1) noise has the registry below. The state
  * image has the class statistics behind the rows of the one-precision image (5 724 rows at 32 parameters and 8
  * precisions: 46 KB per voxel); a run whose image the device cannot hold is refused with -40 and the figure. `launch` is
  * the launcher type of the registry above; it answers -40 for fewer LDS bytes than its own layout for (n_params, n_phis)
@@ -835,7 +835,7 @@ int32_t fabber_vb_find_device_spatial_wave_model(const char *name, fvb_device_sp
  * sizeof(fvb::WaveLayout), another LDS layout) or -27 (duplicate name); unregistering a name that is not registered
  * answers -28. The lifetime rules are those of fabber_vb_register_device_model.
  */
-#define FVB_SPATIAL_WAVE_NOISE_AR1 1  /* reserved */
+#define FVB_SPATIAL_WAVE_NOISE_AR1 1  /* reserved (AR(1) noise: fvb_device_spatial_wave_ar_model below) */
 #define FVB_SPATIAL_WAVE_NOISE_PHIS 2
 typedef struct fvb_device_spatial_wave_noise_model
 {
@@ -854,8 +854,41 @@ const char *fabber_vb_device_spatial_wave_noise_model_name(int32_t i); /* NULL w
 /* A copy of the entry of `name` in *entry and 1; 0 without one. */
 int32_t fabber_vb_find_device_spatial_wave_noise_model(const char *name, fvb_device_spatial_wave_noise_model *entry);
 
+/*
+ * The same family under AR(1) NOISE with one echo and no cross terms (FABBER_DEVICE_SPATIAL_WAVE_AR_MODEL in
+ * include/fabber_device_spatial_wave_ar_model.h): a registry of its own keyed by the name alone, independent of the two
+ * above (an entry needs a body of its name, no other entry). With an entry next to a body of the same name, a
+ * configuration with FVB_MODEL_PLUGIN, FVB_NOISE_AR1, n_phis = 1 and ar_cross_terms = 0 takes these kernels for 1 to
+ * FVB_MAX_PARAMS parameters wherever the registry of fabber_vb_register_device_spatial_noise_model has no AR1 entry for
+ * (name, n_params): the kernel table's name is spatial<NAME,wave,ar1>. Two echoes and cross terms keep -40. The state
+ * image has the rows of the AR(1) lane policy behind the rows of the one-precision image - the alpha posterior, the
+ * diagonal and lag-1 moments, the first and last rows (2 415 rows at 32 parameters: 19 KB per voxel); a run whose image
+ * the device cannot hold is refused with -40 and the figure. `launch` is the launcher type of the registries above; it
+ * answers -40 for fewer LDS bytes than its own layout for n_params needs. lds_probe is the number of doubles of the
+ * family's LDS layout under AR(1) noise at FVB_MAX_PARAMS parameters (fvb::sp_wave_ar_model_layout).
+ * Registration is refused with -86 (descriptor, name or launcher NULL, name too long), -87 (another ABI version), -88
+ * (another sizeof(fvb::SpatialArgs) or sizeof(fvb::WaveLayout), another LDS layout) or -89 (duplicate name);
+ * unregistering a name that is not registered answers -96. The lifetime rules are those of
+ * fabber_vb_register_device_model.
+ */
+typedef struct fvb_device_spatial_wave_ar_model
+{
+    const char *name;
+    int32_t abi_version;        /* FVB_ABI_VERSION the library was compiled against */
+    uint32_t spatial_args_size; /* sizeof(fvb::SpatialArgs) */
+    uint32_t wave_layout_size;  /* sizeof(fvb::WaveLayout) */
+    uint32_t lds_probe;         /* fvb::sp_wave_ar_model_layout(FVB_MAX_PARAMS).n_doubles */
+    fvb_device_spatial_launch_fn launch;
+} fvb_device_spatial_wave_ar_model;
+int32_t fabber_vb_register_device_spatial_wave_ar_model(const fvb_device_spatial_wave_ar_model *model);
+int32_t fabber_vb_unregister_device_spatial_wave_ar_model(const char *name);
+int32_t fabber_vb_device_spatial_wave_ar_model_count(void);
+const char *fabber_vb_device_spatial_wave_ar_model_name(int32_t i); /* NULL when i is out of range */
+/* A copy of the entry of `name` in *entry and 1; 0 without one. */
+int32_t fabber_vb_find_device_spatial_wave_ar_model(const char *name, fvb_device_spatial_wave_ar_model *entry);
+
 /* Which kernel table fabber_vb_run_spatial_* would take for a configuration: "spatial<exp,2>" / "spatial<NAME,P>" /
- * "spatial<NAME,P,ar1>" / "spatial<NAME,wave>" / "spatial<NAME,wave,phis2>" ..., "" where the run would answer -40 or -44 (no kernels for the model /
+ * "spatial<NAME,P,ar1>" / "spatial<NAME,wave>" / "spatial<NAME,wave,phis2>" / "spatial<NAME,wave,ar1>" ..., "" where the run would answer -40 or -44 (no kernels for the model /
  * parameter count / noise model; a library body without a spatial entry for the noise model). Reads n_params, n_phis,
  * noise, ar_cross_terms, need_f, model and device_model. */
 const char *fabber_vb_spatial_kernel_name(const fvb_config *cfg);

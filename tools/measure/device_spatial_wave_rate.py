@@ -26,6 +26,15 @@ with 32 cosine regressors under 2 and under 8 precisions (spatial<linear_spwn,wa
 under white noise with one precision (spatial<linear_spw,wave>), and two exponentials (4 parameters) under pattern 12 on the
 wave kernels (multiexp_spwn), on the lane kernels (multiexp_spwn_both: spatial<multiexp_spwn_both,4,pattern2>, per-level first
 sweep as the others) and under one precision (multiexp_spw) - same process, same job.
+
+--ar: instead of the above, AR(1) noise with one echo (the kernels of include/fabber_device_spatial_wave_ar_model.h,
+tests/plugins/fwdmodel_spatial_wave_ar_models.hip). The sweeps one by one: linear_spwa with 10 cosine regressors
+(spatial<linear_spwa,wave,ar1>) next to linear_spw of the same shape under white noise with one precision, and two
+exponentials (4 parameters) on the wave kernels (multiexp_spwa) and on the lane kernels (multiexp_spwa_both:
+spatial<multiexp_spwa_both,4,ar1>, per-level first sweep as the others), and five exponentials (10 parameters) on the wave
+kernels. Then the whole call for multiexp_spwa with three exponentials (6 parameters) under noise=ar: the device route
+against the host route of the same library - the host route takes AR(1) noise up to 6 parameters and refuses it beyond, so
+there is no host figure at 10.
 """
 import argparse
 import json
@@ -40,6 +49,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 
+import device_spatial_wave_ar_lib
 import device_spatial_wave_lib
 import device_spatial_wave_noise_lib
 from fabber_core_amd import fabber, hiplib, vbabi
@@ -53,6 +63,7 @@ ap.add_argument("--times", type=int, default=100)
 ap.add_argument("--json", default=None)
 ap.add_argument("--skip-host-route", action="store_true")
 ap.add_argument("--patterns", action="store_true")
+ap.add_argument("--ar", action="store_true")
 ap.add_argument("--iters", type=int, default=10)
 args = ap.parse_args()
 
@@ -101,20 +112,23 @@ def linear():
     return y, holder, {"model": "linear_spw", "basis": basis, "param-spatial-priors": "M" + "N" * (P - 1)}, "Parameter_1"
 
 
-def sweeps_one_by_one(name, holder, y, kernels=None):
-    """the device route's a_K update, first sweep and second sweep per iteration, the stream drained after each"""
+def sweeps_one_by_one(name, holder, y, kernels=None, iters=None):
+    """the device route's a_K update, first sweep and second sweep per iteration, the stream drained after each (iters: how
+    many iterations, default --iters; the holder's max_iterations is the caller's)"""
+    iters = iters or ITERS
     kernels = kernels or "spatial<%s,wave>" % name
     assert hiplib.spatial_kernel_name(holder) == kernels, (hiplib.spatial_kernel_name(holder), kernels)
     prob = DeviceProblem(holder, y, "cuda:0")
     prob.run_spatial(sp)  # warm-up: code objects, memory pool
-    assert np.count_nonzero(prob.results()["status"]) < max(1, V // 1000)
+    failed = int(np.count_nonzero(prob.results()["status"]))
+    assert failed < max(1, V // 1000), failed
     ms = dict(ak=[], first=[], second=[])
     t_open = time.perf_counter()
     run = _Run(prob, sp, torch.cuda.current_stream(prob.device))
     torch.cuda.synchronize()
     ms_open = (time.perf_counter() - t_open) * 1e3
     try:
-        for it in range(ITERS):
+        for it in range(iters):
             for what, step in (("ak", None), ("first", lambda: run.sweep_levels(it, -2 ** 62, 2 ** 62)), ("second", lambda: run.sweep_noise(it))):
                 t0 = time.perf_counter()
                 if step is None:
@@ -126,29 +140,29 @@ def sweeps_one_by_one(name, holder, y, kernels=None):
                 ms[what].append((time.perf_counter() - t0) * 1e3)
     finally:
         run.close()
-    out = dict(what="sweeps", route=kernels, voxels=V, timepoints=T, parameters=holder.cfg.n_params, ms_open_with_set_up=ms_open,
+    out = dict(what="sweeps", route=kernels, voxels=V, failed_voxels=failed, timepoints=T, parameters=holder.cfg.n_params, ms_open_with_set_up=ms_open,
                **{"ms_%s_median" % k: float(np.median(v[1:])) for k, v in ms.items()}, **{"ms_%s_all" % k: v for k, v in ms.items()})
     results.append(out)
     print("sweeps  %-28s %7d voxels T=%d P=%d: open + set-up %.1f ms; per iteration (median of iterations 2..%d) a_K %.2f ms, first sweep %.2f ms, "
-          "second sweep %.2f ms" % (out["route"], V, T, holder.cfg.n_params, ms_open, ITERS, out["ms_ak_median"], out["ms_first_median"],
+          "second sweep %.2f ms" % (out["route"], V, T, holder.cfg.n_params, ms_open, iters, out["ms_ak_median"], out["ms_first_median"],
                                     out["ms_second_median"]), flush=True)
     out["ms_iteration_median"] = float(np.median(np.array(ms["ak"][1:]) + np.array(ms["first"][1:]) + np.array(ms["second"][1:])))
     print("sweeps  %-28s per spatial iteration %.2f ms" % (out["route"], out["ms_iteration_median"]), flush=True)
     del prob
 
 
-def whole_calls(name, y, model_opts, first):
+def whole_calls(name, y, model_opts, first, noise="white", kernels=None, library=library, ITERS=ITERS):
     data = np.zeros(SHAPE + (T,), dtype=np.float32)
     data[coords[0], coords[1], coords[2]] = y.T
     secs = {}
-    routes = [("device route", {}, "kernels spatial<%s,wave>" % name)]
+    routes = [("device route", {}, "kernels " + (kernels or "spatial<%s,wave>" % name))]
     if not args.skip_host_route:
         routes.append(("host route", {"host-model": True}, "the model is evaluated on the host"))
     for route, extra, expect in routes:
         # (the device route's first call warms it up - code objects, memory pool - and is repeated; the host route's calls are
         # long against that)
         for iters in ((SHORT, SHORT, ITERS) if not extra else (SHORT, ITERS)):
-            opts = dict({"noise": "white", "method": "spatialvb", "max-iterations": iters, "save-mean": True, "allow-bad-voxels": True},
+            opts = dict({"noise": noise, "method": "spatialvb", "max-iterations": iters, "save-mean": True, "allow-bad-voxels": True},
                         **model_opts, **extra)
             t0 = time.perf_counter()
             res = fabber.run(data, opts, model_libs=[library])
@@ -157,7 +171,7 @@ def whole_calls(name, y, model_opts, first):
             print("call    %-28s %-12s %2d iterations %8.3f s   mean %s %.5f" % (name, route, iters, secs[route, iters], first,
                                                                                 float(np.nanmean(res["mean_" + first]))), flush=True)
         per_it = (secs[route, ITERS] - secs[route, SHORT]) / (ITERS - SHORT)
-        results.append(dict(what="fabber.run", model=name, route=route, voxels=V, timepoints=T, seconds_run_of_10=secs[route, ITERS],
+        results.append(dict(what="fabber.run", model=name, route=route, voxels=V, timepoints=T, iterations_long_run=ITERS, seconds_run_of_10=secs[route, ITERS],
                             seconds_run_of_2=secs[route, SHORT], seconds_per_iteration=per_it))
         print("call    %-28s %-12s %.3f s per iteration (run of %d minus run of %d, / %d)" % (name, route, per_it, ITERS, SHORT, ITERS - SHORT), flush=True)
     if not args.skip_host_route:
@@ -213,6 +227,68 @@ if args.patterns:
                                    ("multiexp_spwn_both", "12", "spatial<multiexp_spwn_both,4,pattern2>")):
         y, holder = biexp_pattern(name, pattern)
         sweeps_one_by_one(name, holder, y, kernels)
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(results, fh, indent=1)
+    sys.exit(0)
+
+def ar_image(white, P, holder):
+    return device_spatial_wave_ar_lib.ar_image(white, P, holder)
+
+
+if args.ar:
+    AR = device_spatial_wave_ar_lib.AR
+    ar_library = device_spatial_wave_ar_lib.build_spatial_wave_ar_library()
+    hiplib.load_model_library(ar_library)
+    os.environ["FVB_SPATIAL_PER_LEVEL"] = "1"  # (the lane route's first sweep as the wave routes': one launch per level)
+    # 10 cosine regressors: one precision on linear_spw, AR(1) on linear_spwa
+    name, y, holder = linear_pattern(10, None)
+    sweeps_one_by_one(name, holder, y)
+    P = 10
+    X = np.cos(np.pi * np.arange(P)[None, :] * (np.arange(T)[:, None] + 0.5) / T)  # (linear_pattern's design and series)
+    kw = dict(param_overrides={"Parameter_1": dict(type="M")})
+    init = ar_image(hiplib.initial_mvn(vbabi.build_config(vbabi.MODEL_LINEAR, V, T, design=X, **kw), y), P,
+                    vbabi.build_config(vbabi.MODEL_LINEAR, V, T, design=X, **kw, **AR))
+    n = P + 3
+    for k in range(P):
+        init[n * (n + 1) // 2 + k] = 1.0 / (k + 1)
+    holder = vbabi.build_config(vbabi.MODEL_PLUGIN, V, T, device_model="linear_spwa", constants=X, init_mvn=init, max_iterations=ITERS,
+                                params=vbabi.model_parameter_defaults(vbabi.MODEL_LINEAR, n_basis=P), **kw, **AR)
+    sweeps_one_by_one("linear_spwa", holder, y, "spatial<linear_spwa,wave,ar1>")
+
+    # The exponential fits under AR(1) noise run EXP_ITERS iterations: with more, most voxels of these series (white noise
+    # in the data) stop with a status - in the CPU oracle as on the device, 80 % of them after 10 iterations of the two
+    # exponentials - and leave the sweeps, so a later iteration times another problem.
+    EXP_ITERS = min(ITERS, 4)
+
+    def exp_ar(name, num, dt=0.006):
+        rates, amps = np.array([0.5, 3.0, 12.0, 40.0, 150.0])[:num], np.array([1.0, 0.8, 0.6, 0.4, 0.3])[:num]
+        if num == 2:
+            rates, amps = np.array([0.5, 12.0]), np.array([1.0, 0.6])
+        t = np.arange(T) * dt
+        y = (sum(amps[i] * scale[None, :] * np.exp(-rates[i] * t)[:, None] for i in range(num))
+             + np.random.default_rng(4).normal(0, 0.02, (T, V))).astype(np.float32)
+        kw = dict(num_exps=num, dt=dt, param_overrides={"amp1": dict(type="M")})
+        init = ar_image(hiplib.initial_mvn(vbabi.build_config(vbabi.MODEL_EXP, V, T, **kw), y), 2 * num,
+                        vbabi.build_config(vbabi.MODEL_EXP, V, T, **kw, **AR))
+        n = 2 * num + 3
+        for i in range(num):
+            init[n * (n + 1) // 2 + 2 * i], init[n * (n + 1) // 2 + 2 * i + 1] = np.log(amps[i]), np.log(rates[i])
+        return y, vbabi.build_config(vbabi.MODEL_PLUGIN, V, T, device_model=name, init_mvn=init, max_iterations=EXP_ITERS,
+                                     params=vbabi.model_parameter_defaults(vbabi.MODEL_EXP, num_exps=num), **kw, **AR)
+
+    for name, kernels in (("multiexp_spwa", "spatial<multiexp_spwa,wave,ar1>"), ("multiexp_spwa_both", "spatial<multiexp_spwa_both,4,ar1>")):
+        y, holder = exp_ar(name, 2)
+        sweeps_one_by_one(name, holder, y, kernels, iters=EXP_ITERS)
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(results, fh, indent=1)
+    y, holder = exp_ar("multiexp_spwa", 5)
+    sweeps_one_by_one("multiexp_spwa", holder, y, "spatial<multiexp_spwa,wave,ar1>", iters=EXP_ITERS)
+    y, holder = exp_ar("multiexp_spwa", 3)
+    sweeps_one_by_one("multiexp_spwa", holder, y, "spatial<multiexp_spwa,wave,ar1>", iters=EXP_ITERS)
+    whole_calls("multiexp_spwa", y, {"model": "multiexp_spwa", "num-exps": 3, "dt": 0.006, "param-spatial-priors": "M" + "N" * 5}, "amp1",
+                noise="ar", kernels="spatial<multiexp_spwa,wave,ar1>", library=ar_library, ITERS=EXP_ITERS)
     if args.json:
         with open(args.json, "w") as fh:
             json.dump(results, fh, indent=1)
