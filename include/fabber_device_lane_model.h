@@ -28,8 +28,41 @@
  * patterns of 2 to 4 precisions have lane kernels of their own, which a library compiles with a line of
  * fabber_device_lane_noise_model.h (FABBER_DEVICE_LANE_NOISE_MODEL); without that line they run the wave kernels of
  * FABBER_DEVICE_MODEL, as everything else does - two echoes, 5 to 8 precisions, other parameter counts, small volumes.
- * The body is evaluated pointwise, as in the wave kernels (a library cannot supply a sweep), and the kernel's name is
- * lane<NAME,P> / lane<NAME,P,F>.
+ * The kernel's name is lane<NAME,P> / lane<NAME,P,F>.
+ *
+ * A SWEEP OF THE BODY'S OWN (optional). A linearisation needs 2 P + 1 predictions per timepoint: g = f(p) and, for every
+ * parameter i, f with entry i replaced by p2[i] and by p3[i]. Without more from the body the kernels call eval for each of
+ * them. A body whose predictions share work ALONG t (a geometric sequence, a running sum, a convolution built up sample
+ * by sample) can say so with a nested member template, and every lane family of these headers - white noise, AR(1), noise
+ * patterns, the spatial lane kernels - then linearises through it:
+ *
+ *     template <int P> struct Sweep
+ *     {
+ *         // members: the state of ONE linearisation of ONE voxel; it lives in registers across the pass
+ *         __device__ __forceinline__ void init(const fvb::ModelArgs &a, const double (&p)[P], const double (&p2)[P],
+ *             const double (&p3)[P]);
+ *         // g = f(p); f2[i] / f3[i] = f(p with entry i replaced by p2[i] / p3[i]), all at timepoint t
+ *         __device__ __forceinline__ void step(const fvb::ModelArgs &a, int t, bool exact, const double (&p)[P],
+ *             const double (&p2)[P], const double (&p3)[P], double &g, double (&f2)[P], double (&f3)[P]);
+ *     };
+ *
+ * The contract (fvb::LibrarySweep below is the engine's side of it):
+ *   - init comes first; after it step is called for t = 0, 1, 2, ... in this order, every timepoint once (a masked
+ *     timepoint included), with the p, p2, p3 that init saw;
+ *   - `exact` is wave-uniform. It is true at the first step after init; at EVERY step of a pass the engine wants evaluated
+ *     as precisely as the body can (the first precise_passes linearisations of a run and the passes that form a Jacobian
+ *     made that way again); otherwise at least once in every 8 consecutive timepoints (FVB_EXP_RESYNC: where t is a
+ *     multiple of 8);
+ *   - an exact step returns what 2 P + 1 calls of eval return, to rounding; a step that is not exact may use what the step
+ *     at t - 1 left (what a recurrence adds in rounding is bounded by the 7 steps between two exact ones);
+ *   - the sweep is deterministic: a linearisation that is formed again (the residual passes) gives the same values;
+ *   - the body hands over no derivatives: the engine forms J from the two perturbed sums, (f2[i] - f3[i]) * rden[i], as
+ *     for every model (vb_models.h says why a structured quotient was measured and dropped);
+ *   - the sweep reads a.consts and fvb::supp_at as eval does, with the same checks of n_consts / n_supp.
+ * Everything else evaluates the body pointwise through eval, so a body with a sweep still needs a correct eval: the rescue
+ * passes of the lane kernels, the wave-per-voxel kernels, the NLLS minimisers, the result-image and initial-posterior
+ * kernels. A body without the member is evaluated pointwise throughout, by the same kernel code as before the member
+ * existed. Registration is the same macro line either way.
  *
  * The macro, at namespace scope:
  *   - instantiates the eight white-noise lane kernels for the body (in-place feed, float tiles and double tiles, each
@@ -47,10 +80,78 @@
 #include "fabber_device_registration.h"
 #include "../fabber_core_amd/csrc/vb_lane_launch.h"
 
+#include <type_traits>
+
 namespace fvb
 {
-// the body as a model of the lane kernels (vb_models.h): P a constant, the pointwise sweep, the initial posterior from
-// the host (init_mvn)
+// does the body bring `template <int P> struct Sweep`?
+template <class Eval, int P, class = void>
+struct body_has_sweep : std::false_type
+{
+};
+template <class Eval, int P>
+struct body_has_sweep<Eval, P, std::void_t<typename Eval::template Sweep<P>>> : std::true_type
+{
+};
+
+// The body's sweep behind the sweep interface of the lane kernels (vb_models.h; ExpModel<P>::Sweep is the built-in model
+// of it). When a step is exact is decided here, from what the kernels ask: every step of a precise pass, and otherwise
+// the timepoints that are multiples of FVB_EXP_RESYNC - the kernels' streaming loop (recentre_tiles) knows those at compile
+// time and says so through step_fast<EXACT>. init clears the flag because one call site (the AR(1) residual pass) never
+// sets it. step_acc (the half-ulp exp of the spatial set-up kernels) is asked of the exponential model only.
+template <class Eval, int P>
+struct LibrarySweep
+{
+    typename Eval::template Sweep<P> body;
+    bool precise; // every step exact (wave-uniform)
+    __device__ __forceinline__ void init(const ModelArgs &a, const double (&tp)[P], const double (&tp2)[P], const double (&tp3)[P])
+    {
+        precise = false;
+        body.init(a, tp, tp2, tp3);
+    }
+    __device__ __forceinline__ void set_precise(bool p)
+    {
+        precise = p;
+    }
+    __device__ __forceinline__ void eval(const ModelArgs &a, int t, const double (&tp)[P], const double (&tp2)[P], const double (&tp3)[P],
+        double &g, double (&f2)[P], double (&f3)[P])
+    {
+        body.step(a, t, precise || (t % FVB_EXP_RESYNC) == 0, tp, tp2, tp3, g, f2, f3);
+    }
+    // J_i = (f2_i - f3_i) * rden_i from the two perturbed sums, as PointwiseSweep forms it
+    __device__ __forceinline__ void jacobian(const double (&f2)[P], const double (&f3)[P], const double (&rden)[P], double (&J)[P])
+    {
+        FVB_MODEL_FP
+#pragma unroll
+        for (int i = 0; i < P; i++)
+            J[i] = (f2[i] - f3[i]) * rden[i];
+    }
+    __device__ __forceinline__ void eval_jac(const ModelArgs &a, int t, const double (&tp)[P], const double (&tp2)[P], const double (&tp3)[P],
+        const double (&rden)[P], double &g, double (&J)[P])
+    {
+        double f2[P], f3[P];
+        eval(a, t, tp, tp2, tp3, g, f2, f3);
+        jacobian(f2, f3, rden, J);
+    }
+    template <bool EXACT>
+    __device__ __forceinline__ void step_fast(const ModelArgs &a, int t, const double (&tp)[P], const double (&tp2)[P], const double (&tp3)[P],
+        const double (&rden)[P], double &g, double (&J)[P])
+    {
+        double f2[P], f3[P];
+        body.step(a, t, EXACT, tp, tp2, tp3, g, f2, f3);
+        jacobian(f2, f3, rden, J);
+    }
+    __device__ __forceinline__ void step_any(const ModelArgs &a, int t, const double (&tp)[P], const double (&tp2)[P], const double (&tp3)[P],
+        const double (&rden)[P], double &g, double (&J)[P], bool prec)
+    {
+        double f2[P], f3[P];
+        body.step(a, t, prec || (t % FVB_EXP_RESYNC) == 0, tp, tp2, tp3, g, f2, f3);
+        jacobian(f2, f3, rden, J);
+    }
+};
+
+// the body as a model of the lane kernels (vb_models.h): P a constant, the body's sweep or else the pointwise one, the
+// initial posterior from the host (init_mvn)
 template <class Eval>
 struct LibraryLane
 {
@@ -59,7 +160,8 @@ struct LibraryLane
     {
         static constexpr bool host_evaluated = false;
         static constexpr int model_id = FVB_MODEL_PLUGIN;
-        typedef PointwiseSweep<Model<P>, P> Sweep;
+        // (LibrarySweep<Eval, P> is only named here: it is not instantiated for a body without the member)
+        typedef std::conditional_t<body_has_sweep<Eval, P>::value, LibrarySweep<Eval, P>, PointwiseSweep<Model<P>, P>> Sweep;
         static __device__ __forceinline__ double eval(const ModelArgs &a, int t, const double (&p)[P])
         {
             return Eval::eval(a, P, t, p);
