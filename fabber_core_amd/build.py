@@ -169,6 +169,7 @@ def _compile_host_one(args):
     h.update(" ".join(HOST_FLAGS).encode())
     deps = [src] + _headers() + [os.path.join(d, f) for d in (os.path.join(HOST_DIR, "fabber_core"), os.path.join(HOST_DIR, "armawrap"))
                                  for f in sorted(os.listdir(d))]
+    deps += [os.path.join(HOST_DIR, f) for f in sorted(os.listdir(HOST_DIR)) if f.endswith(".h")]  # the library's internal headers
     deps.append(os.path.join(os.path.dirname(HERE), "include", "fabber_capi.h"))
     for f in deps:
         with open(f, "rb") as fh:

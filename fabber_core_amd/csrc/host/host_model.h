@@ -7,25 +7,30 @@
 #include "fwdmodel.h"
 #include "rundata.h"
 
+#include "../../../include/fabber_vb.h"
+
 #include <memory>
 #include <string>
 #include <vector>
 
 struct HostModelContext
 {
-    void *self;
     FwdModel *model;
     FabberRunData *rundata;
     const NEWMAT::Matrix *data, *coords, *suppdata;
     int T, P;
     std::string error;
     std::vector<FwdModel *> models; // [0] = the technique's own instance, the rest are per-thread copies
+    std::vector<std::unique_ptr<FwdModel> > copies; // ... which it owns
 };
 
-/** One model instance per host thread (option host-model-threads); fills ctx.models and ctx.data. Returns the count. */
-int host_model_instances(HostModelContext &ctx, std::vector<std::unique_ptr<FwdModel> > &copies, FwdModel *model, FabberRunData &rundata,
-    EasyLog *log);
+/** Before the engine call: one model instance per host thread (option host-model-threads; fills ctx.models and ctx.data),
+ *  and the series as the matrix they read. Returns the count. */
+int host_model_instances(HostModelContext &ctx, fvb_config &cfg, const void *&series, EasyLog *log);
 
 /** fvb_linearise_fn: LinearizedFwdModel::ReCentre (fwdmodel_linear.cc:126-182) for the active voxels, shared out over
  *  the instances; user = HostModelContext*. An exception of the model ends up in ctx.error, return value 1. */
 int32_t host_model_linearise(void *user, int32_t n_active, const int32_t *ids, const double *means, double *lin);
+
+/** After the call: the model's own exception where the callback reported one (the engine answers -54 then). */
+void host_model_rethrow(const HostModelContext &ctx, int rc);

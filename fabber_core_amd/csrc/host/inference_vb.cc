@@ -11,17 +11,15 @@
 #include "tools.h"
 
 #include "convergence.h"
-#include "priors.h"
+#include "engine_binding.h"
 #include "host_model.h"
+#include "priors.h"
 #include "version.h"
-
-#include "../../../include/fabber_vb.h"
 
 #include <cstring>
 #include <math.h>
 #include <algorithm>
 #include <memory>
-#include <thread>
 
 using namespace std;
 using NEWMAT::ColumnVector;
@@ -99,25 +97,7 @@ void InferenceTechnique::SaveResults(FabberRunData &rundata) const
 // ---------------------------------------------------------------------------------------------
 // Vb
 // ---------------------------------------------------------------------------------------------
-struct Vb::EngineStorage
-{
-    fvb_config cfg;
-    Matrix design;                           // T x P row-major = engine layout
-    vector<unsigned char> phi_index;         // per timepoint
-    vector<vector<double> > image_priors;    // per parameter
-    Matrix init_mvn;                         // continue-from-mvn
-    vector<Parameter> params;
-    vector<string> model_outputs;
-    bool has_device_model;
-    bool library_device_model;     // ... and it is a body the model's library registered (FVB_MODEL_PLUGIN)
-    std::vector<double> constants; // its constants (fvb_config.model_consts)
-    bool uses_suppdata;            // ... and it reads the voxels' supplementary data (fvb_config.model_supp)
-    // more than FVB_MAX_PARAMS parameters: the per-parameter entries as a table (fvb_config.params_ext)
-    vector<int32_t> wide_transform, wide_type;
-    vector<double> wide_mean, wide_var, wide_prec, wide_post_mean, wide_post_var;
-    vector<const double *> wide_images;
-    fvb_param_table wide;
-};
+struct Vb::EngineStorage : EngineBinding { struct Run; };
 
 static OptionSpec VB_OPTIONS[] = {
     { "noise", OPT_STR, "Noise model to use (white or ar1)", OPT_REQ, "" },
@@ -223,161 +203,23 @@ bool Vb::IsSpatial(FabberRunData &rundata) const
     return false;
 }
 
-// The main series as the engine reads it: float32 where the run data holds it so (every volume set through the C
-// ABI, FabberRunData::SetVoxelDataF32), else the double matrix. as_matrix: the caller needs the matrix anyway (a
-// model evaluated on the host is handed NEWMAT columns).
-const void *engine_series(FabberRunData &rundata, bool as_matrix, int32_t &data_f64, int &rows, int &cols)
+// a body the model's library supplies counts when the library has registered it with the engine
+static bool engine_lists_body(const fvb_config &, const string &body)
 {
-    const float *f32 = as_matrix ? NULL : rundata.GetMainVoxelDataF32(rows, cols);
-    if (f32)
+    bool registered = false;
+    for (int i = 0; i < fabber_vb_device_model_count() && !registered; i++)
     {
-        data_f64 = 0;
-        return f32;
+        const char *name = fabber_vb_device_model_name(i);
+        registered = name && body == name;
     }
-    const Matrix &data = rundata.GetMainVoxelData();
-    rows = data.Nrows();
-    cols = data.Ncols();
-    data_f64 = 1; // (rows = timepoints, columns = voxels)
-    return data.Store();
+    return registered;
 }
 
-// The run's supplementary data as a library's device body reads it (DeviceModelSpec::uses_suppdata): the matrix is
-// timepoints x voxels with the voxel fastest, which is the engine's layout, so its store is handed over as it is - the
-// run data keeps it for the run. Without one value per voxel there is none (NULL, 0 rows): the body's own bound check
-// then stops every voxel with the non-finite-offset status, as with too few constants.
-void engine_suppdata(FabberRunData &rundata, fvb_config &cfg)
+// noise-initial-prior / noise-initial-posterior: ONE distribution from a matrix file for every voxel
+// (Vb::InitializeNoiseFromParam, inference_vb.cc:132-142 -> NoiseParams::InputFromMVN); for white noise that is
+// a Gamma per precision from its mean and variance (noisemodel_white.cc:70-79, dist_gamma.cc:29-33)
+static void noise_distributions_from_files(FabberRunData &rundata, fvb_config &cfg, EasyLog *m_log)
 {
-    const Matrix &supp = rundata.GetVoxelSuppData();
-    const bool per_voxel = cfg.n_voxels > 0 && supp.Ncols() == cfg.n_voxels && supp.Nrows() > 0;
-    cfg.model_supp = per_voxel ? supp.Store() : NULL;
-    cfg.n_model_supp = per_voxel ? supp.Nrows() : 0;
-}
-
-void Vb::BuildEngineConfig(FabberRunData &rundata, fvb_config &cfg)
-{
-    EngineStorage &st = *m_store;
-    memset(&cfg, 0, sizeof(cfg));
-    cfg.abi_version = FVB_ABI_VERSION;
-    {
-        int rows = 0, cols = 0;
-        (void)engine_series(rundata, false, cfg.data_f64, rows, cols);
-        cfg.n_voxels = cols;
-        cfg.n_times = rows;
-    }
-
-    // ---- model ----
-    st.params.clear();
-    m_model->GetParameters(rundata, st.params);
-    const int P = (int)st.params.size();
-    if (P > FVB_MAX_PARAMS_EXT)
-        throw FabberInternalError("Models with more than " + stringify(FVB_MAX_PARAMS_EXT) + " parameters are not supported by the MI355X engine");
-    cfg.n_params = P;
-    // beyond FVB_MAX_PARAMS the per-parameter entries travel as a table (the wave-per-voxel kernels take such problems:
-    // voxelwise VB, white or AR(1) noise, a built-in model - the engine says so where that is not the case)
-    const bool wide = P > FVB_MAX_PARAMS;
-    if (wide)
-    {
-        st.wide_transform.assign(P, 0);
-        st.wide_type.assign(P, 0);
-        st.wide_mean.assign(P, 0);
-        st.wide_var.assign(P, 0);
-        st.wide_prec.assign(P, 0);
-        st.wide_post_mean.assign(P, 0);
-        st.wide_post_var.assign(P, 0);
-        st.wide_images.assign(P, (const double *)NULL);
-    }
-    DeviceModelSpec spec;
-    // A model without a device body (any model library written for the reference), or any model
-    // when host-model is set, is evaluated on the host: 2P+1 Evaluate calls per voxel and
-    // re-centre, everything else on the GPU (fabber_vb_run_hostmodel_host).
-    st.has_device_model = m_model->GetDeviceModel(spec) && !rundata.GetBool("host-model");
-    // a body the model's library supplies counts when the library has registered it with the engine
-    st.library_device_model = st.has_device_model && !spec.device_model.empty();
-    if (st.library_device_model)
-    {
-        bool registered = false;
-        for (int i = 0; i < fabber_vb_device_model_count() && !registered; i++)
-        {
-            const char *name = fabber_vb_device_model_name(i);
-            registered = name && spec.device_model == name;
-        }
-        if (!registered || spec.device_model.size() >= sizeof(cfg.device_model))
-            st.has_device_model = st.library_device_model = false;
-    }
-    if (!st.has_device_model)
-    {
-        spec = DeviceModelSpec();
-        spec.model = FVB_MODEL_HOSTJAC;
-    }
-    if (st.library_device_model)
-    {
-        spec.model = FVB_MODEL_PLUGIN;
-        strncpy(cfg.device_model, spec.device_model.c_str(), sizeof(cfg.device_model) - 1);
-        st.constants = spec.constants;
-        cfg.model_consts = st.constants.empty() ? NULL : st.constants.data();
-        cfg.n_model_consts = (int32_t)st.constants.size();
-        if (spec.uses_suppdata)
-            engine_suppdata(rundata, cfg);
-    }
-    st.uses_suppdata = st.library_device_model && spec.uses_suppdata;
-    cfg.model = spec.model;
-    for (int i = 0; i < 4; i++)
-    {
-        cfg.model_iopt[i] = spec.iopt[i];
-        cfg.model_dopt[i] = spec.dopt[i];
-    }
-    if (spec.model == FVB_MODEL_LINEAR)
-    {
-        if (spec.design.Nrows() != cfg.n_times && cfg.n_voxels > 0)
-            throw InvalidOptionValue("basis", stringify(spec.design.Nrows()) + " rows",
-                "Design matrix length does not match the data (" + stringify(cfg.n_times) + " timepoints)");
-        st.design = spec.design;
-        cfg.design = st.design.Store();
-    }
-
-    // ---- parameters / priors ----
-    st.image_priors.assign(P, vector<double>());
-    for (int k = 0; k < P; k++)
-    {
-        const Parameter &p = st.params[k];
-        (wide ? st.wide_transform[k] : cfg.transform[k]) = p.transform->DeviceCode();
-        (wide ? st.wide_type[k] : cfg.prior_type[k]) = Prior::DeviceCode(p.prior_type);
-        (wide ? st.wide_mean[k] : cfg.prior_mean[k]) = p.prior.mean();
-        (wide ? st.wide_var[k] : cfg.prior_var[k]) = p.prior.var();
-        (wide ? st.wide_prec[k] : cfg.prior_prec[k]) = p.prior.prec();
-        (wide ? st.wide_post_mean[k] : cfg.post_mean[k]) = p.post.mean();
-        (wide ? st.wide_post_var[k] : cfg.post_var[k]) = p.post.var();
-        if (p.prior_type == PRIOR_IMAGE)
-        {
-            const Matrix &img = rundata.GetVoxelData(p.options.find("image")->second);
-            if (img.Ncols() != cfg.n_voxels || img.Nrows() < 1)
-                throw InvalidOptionValue("image prior", p.name, "Image prior must have one value per voxel");
-            st.image_priors[k].resize(cfg.n_voxels);
-            for (int v = 0; v < cfg.n_voxels; v++)
-                st.image_priors[k][v] = img.at0(0, v);
-            (wide ? st.wide_images[k] : cfg.image_prior[k]) = st.image_priors[k].data();
-        }
-    }
-
-    if (wide)
-    {
-        st.wide.transform = st.wide_transform.data();
-        st.wide.prior_type = st.wide_type.data();
-        st.wide.prior_mean = st.wide_mean.data();
-        st.wide.prior_var = st.wide_var.data();
-        st.wide.prior_prec = st.wide_prec.data();
-        st.wide.post_mean = st.wide_post_mean.data();
-        st.wide.post_var = st.wide_post_var.data();
-        st.wide.image_prior = st.wide_images.data();
-        cfg.params_ext = &st.wide;
-    }
-
-    // ---- noise ----
-    m_noise->ConfigureEngine(cfg, cfg.n_times, st.phi_index);
-    cfg.phi_index = st.phi_index.empty() ? NULL : st.phi_index.data();
-    // noise-initial-prior / noise-initial-posterior: ONE distribution from a matrix file for every voxel
-    // (Vb::InitializeNoiseFromParam, inference_vb.cc:132-142 -> NoiseParams::InputFromMVN); for white noise that is
-    // a Gamma per precision from its mean and variance (noisemodel_white.cc:70-79, dist_gamma.cc:29-33)
     for (const char *key : { "noise-initial-prior", "noise-initial-posterior" })
     {
         const string filename = rundata.GetStringDefault(key, "modeldefault");
@@ -446,8 +288,11 @@ void Vb::BuildEngineConfig(FabberRunData &rundata, fvb_config &cfg)
             (prior ? cfg.noise_prior_c : cfg.noise_post_c)[i] = c;
         }
     }
+}
 
-    // ---- convergence ----
+// The convergence detector. Returns whether the free energy is computed: it or an output reads it (inference_vb.cc:242).
+static bool convergence_section(FabberRunData &rundata, fvb_config &cfg, bool outputs_read_f, bool save_history)
+{
     std::unique_ptr<ConvergenceDetector> conv(
         ConvergenceDetector::NewFromName(rundata.GetStringDefault("convergence", "maxits")));
     conv->Initialize(rundata);
@@ -455,36 +300,54 @@ void Vb::BuildEngineConfig(FabberRunData &rundata, fvb_config &cfg)
     cfg.max_iterations = conv->MaxIterations();
     cfg.max_trials = conv->MaxTrials();
     cfg.min_fchange = conv->MinFChange();
-    m_needF = conv->UseF() || m_printF || m_saveF || m_saveFsHistory; // inference_vb.cc:242
-    cfg.need_f = m_needF ? 1 : 0;
+    const bool need_f = conv->UseF() || outputs_read_f;
+    cfg.need_f = need_f ? 1 : 0;
     // every iteration pushes one value and the end of the voxel one more; trial mode and LM can
     // run more iterations than max-iterations
-    cfg.f_history_rows = m_saveFsHistory ? (cfg.max_iterations + 2) * (conv->UseF() ? 12 : 1) : 0;
+    cfg.f_history_rows = save_history ? (cfg.max_iterations + 2) * (conv->UseF() ? 12 : 1) : 0;
+    return need_f;
+}
 
-    // ---- resume ----
-    bool continue_from_mvn = true;
+// continue-from-mvn: the given image is the initial posterior (n_noise: the noise model's entries in it)
+static void resume_section(FabberRunData &rundata, EngineBinding &st, int n_noise, EasyLog *m_log)
+{
+    fvb_config &cfg = st.cfg;
     try
     {
         st.init_mvn = rundata.GetVoxelData("continue-from-mvn");
     }
     catch (DataNotFound &)
     {
-        continue_from_mvn = false;
+        return;
     }
-    if (continue_from_mvn)
-    {
-        LOG << "Vb::Continuing from MVN" << endl;
-        const int rows = fabber_vb_mvn_rows(P + m_noise_params);
-        if (st.init_mvn.Nrows() != rows)
-            throw FabberRunDataError("MVNDist::Load  - Incorrect number of rows for an MVN input");
-        if (st.init_mvn.Ncols() != cfg.n_voxels)
-            throw FabberRunDataError("MVNDist::Load - MVN input has the wrong number of voxels");
-        for (int v = 0; v < cfg.n_voxels; v++)
-            if (st.init_mvn.at0(rows - 1, v) != 1)
-                throw FabberRunDataError("MVNDist::Load - Voxel data does not contain a valid MVN - last value != 1");
-        cfg.init_mvn = st.init_mvn.Store();
-        rundata.GetStringDefault("continue-from-params", "");
-    }
+    LOG << "Vb::Continuing from MVN" << endl;
+    const int rows = fabber_vb_mvn_rows(cfg.n_params + n_noise);
+    if (st.init_mvn.Nrows() != rows)
+        throw FabberRunDataError("MVNDist::Load  - Incorrect number of rows for an MVN input");
+    if (st.init_mvn.Ncols() != cfg.n_voxels)
+        throw FabberRunDataError("MVNDist::Load - MVN input has the wrong number of voxels");
+    for (int v = 0; v < cfg.n_voxels; v++)
+        if (st.init_mvn.at0(rows - 1, v) != 1)
+            throw FabberRunDataError("MVNDist::Load - Voxel data does not contain a valid MVN - last value != 1");
+    cfg.init_mvn = st.init_mvn.Store();
+    rundata.GetStringDefault("continue-from-params", "");
+}
+
+// (cfg is the store's own block: everything it points into lives next to it)
+void Vb::BuildEngineConfig(FabberRunData &rundata, fvb_config &cfg)
+{
+    EngineStorage &st = *m_store;
+    st.Begin(m_model, rundata);
+    // A model without a device body (any model library written for the reference), or any model
+    // when host-model is set, is evaluated on the host: 2P+1 Evaluate calls per voxel and
+    // re-centre, everything else on the GPU (fabber_vb_run_hostmodel_host).
+    st.BindModel(m_model, rundata, &engine_lists_body);
+    st.BindParameters(rundata);
+    m_noise->ConfigureEngine(cfg, cfg.n_times, st.phi_index);
+    cfg.phi_index = st.phi_index.empty() ? NULL : st.phi_index.data();
+    noise_distributions_from_files(rundata, cfg, m_log);
+    m_needF = convergence_section(rundata, cfg, m_printF || m_saveF || m_saveFsHistory, m_saveFsHistory);
+    resume_section(rundata, st, m_noise_params, m_log);
 }
 
 // ---- host-evaluated models ----------------------------------------------------------------------
@@ -504,9 +367,7 @@ void Vb::BuildInitialMvn(FabberRunData &rundata, fvb_config &cfg)
     const Matrix &supp = rundata.GetVoxelSuppData();
     Matrix &img = m_store->init_mvn;
     img.ReSize(rows, V);
-    for (int r = 0; r < rows; r++)
-        for (int v = 0; v < V; v++)
-            img.at0(r, v) = 0;
+    img = 0;
     for (int v = 0; v < V; v++)
     {
         if (supp.Ncols() == V)
@@ -546,119 +407,234 @@ void Vb::BuildInitialMvn(FabberRunData &rundata, fvb_config &cfg)
     cfg.init_mvn = img.Store();
 }
 
-// one model instance per host thread (host-model-threads, default: the hardware's, at most 16): a FwdModel holds the
-// current voxel's data, so instances cannot be shared
-int host_model_instances(HostModelContext &ctx, std::vector<std::unique_ptr<FwdModel> > &copies, FwdModel *model, FabberRunData &rundata,
-    EasyLog *log)
-{
-    int nthreads = rundata.GetIntDefault("host-model-threads", 0, 0, 256);
-    if (nthreads == 0)
-        nthreads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
-    ctx.models.push_back(model);
-    for (int k = 1; k < nthreads; k++)
-    {
-        copies.emplace_back(FwdModel::NewFromName(rundata.GetString("model")));
-        copies.back()->SetLogger(log);
-        copies.back()->Initialize(rundata);
-        vector<Parameter> tmp;
-        copies.back()->GetParameters(rundata, tmp); // resolves the transforms EvaluateFabber applies
-        ctx.models.push_back(copies.back().get());
-    }
-    ctx.data = &rundata.GetMainVoxelData();
-    return nthreads;
-}
-
-// LinearizedFwdModel::ReCentre (fwdmodel_linear.cc:126-182) for active voxels [a0, a1) with one model instance
-static void linearise_range(HostModelContext &cx, FwdModel *model, int a0, int a1, const int32_t *ids, const double *means, double *lin)
-{
-    const int T = cx.T, P = cx.P;
-    const bool have_supp = cx.suppdata->Ncols() == cx.data->Ncols();
-    ColumnVector centre(P), pert(P), g, f2, f3;
-    for (int a = a0; a < a1; a++)
-    {
-        const int v = ids[a];
-        if (have_supp)
-            model->PassData(v + 1, ColumnVector(cx.data->Column(v + 1)), ColumnVector(cx.coords->Column(v + 1)),
-                ColumnVector(cx.suppdata->Column(v + 1)));
-        else
-            model->PassData(v + 1, ColumnVector(cx.data->Column(v + 1)), ColumnVector(cx.coords->Column(v + 1)));
-        for (int i = 0; i < P; i++)
-            centre(i + 1) = means[(size_t)a * P + i];
-        double *out = lin + (size_t)a * T * (P + 1);
-        model->EvaluateFabber(centre, g, "");
-        if (g.Nrows() != T)
-            throw FabberInternalError("Model returned " + stringify(g.Nrows()) + " timepoints, data has " + stringify(T));
-        for (int t = 0; t < T; t++)
-            out[t] = g(t + 1);
-        for (int i = 0; i < P; i++)
-        {
-            double delta = centre(i + 1) * 1e-5; // :157-161
-            if (delta < 0)
-                delta = -delta;
-            if (delta < 1e-10)
-                delta = 1e-10;
-            pert = centre;
-            pert(i + 1) = centre(i + 1) + delta;
-            const double c2 = pert(i + 1);
-            model->EvaluateFabber(pert, f2, "");
-            pert(i + 1) = centre(i + 1) - delta;
-            const double c3 = pert(i + 1);
-            model->EvaluateFabber(pert, f3, "");
-            for (int t = 0; t < T; t++)
-                out[T + (size_t)t * P + i] = (f2(t + 1) - f3(t + 1)) / (c2 - c3);
-        }
-    }
-}
-
-// fvb_linearise_fn: the active voxels shared out over the host threads, one model instance each
-// (a FwdModel holds the current voxel's data, so instances cannot be shared)
 int32_t Vb::LineariseCallback(void *user, int32_t n_active, const int32_t *ids, const double *means, double *lin)
 {
     return host_model_linearise(user, n_active, ids, means, lin);
 }
 
-int32_t host_model_linearise(void *user, int32_t n_active, const int32_t *ids, const double *means, double *lin)
-{
-    HostModelContext &cx = *static_cast<HostModelContext *>(user);
-    const int nthreads = std::max(1, std::min((int)cx.models.size(), n_active / 64 + 1));
-    std::vector<std::string> errors(nthreads);
-    auto work = [&](int k) {
-        try
-        {
-            const int a0 = (int)((long long)n_active * k / nthreads), a1 = (int)((long long)n_active * (k + 1) / nthreads);
-            linearise_range(cx, cx.models[k], a0, a1, ids, means, lin);
-        }
-        catch (std::exception &e)
-        {
-            errors[k] = e.what();
-        }
-        catch (...)
-        {
-            errors[k] = "unknown exception in the model";
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int k = 1; k < nthreads; k++)
-        pool.emplace_back(work, k);
-    work(0);
-    for (size_t k = 0; k < pool.size(); k++)
-        pool[k].join();
-    for (int k = 0; k < nthreads; k++)
-        if (errors[k] != "")
-        {
-            cx.error = errors[k];
-            return 1;
-        }
-    return 0;
-}
-
-// The engine's per-iteration callback carries no context pointer: the run data whose
-// ProgressCheck should hear about spatial iterations (inference_vb.cc:610) is kept per thread.
+// The engine's per-iteration callback carries no context pointer: the run data whose ProgressCheck should hear
+// about spatial iterations (inference_vb.cc:610) is kept per thread, for as long as a spatial run's scope lasts.
 static thread_local FabberRunData *s_progress_rundata = NULL;
 static void spatial_progress(int it, int maxits)
 {
     if (s_progress_rundata)
         s_progress_rundata->Progress(it, maxits);
+}
+struct SpatialProgressScope
+{
+    explicit SpatialProgressScope(FabberRunData &rundata) { s_progress_rundata = &rundata; }
+    ~SpatialProgressScope() { s_progress_rundata = NULL; }
+};
+
+// devices=0,1,...: the list; empty for "" and for "all"
+static vector<int32_t> parse_devices(const string &devices_opt)
+{
+    vector<int32_t> device_list;
+    if (devices_opt == "" || devices_opt == "all")
+        return device_list;
+    for (size_t begin = 0, end; begin <= devices_opt.size(); begin = end + 1)
+    {
+        end = std::min(devices_opt.find(',', begin), devices_opt.size());
+        if (end == begin)
+            throw InvalidOptionValue("devices", devices_opt, "Must be 'all' or a comma-separated list of device indices");
+        device_list.push_back(convertTo<int>(devices_opt.substr(begin, end - begin)));
+    }
+    return device_list;
+}
+
+// One DoCalculations past its set-up: what the three routes to the engine share. Each route answers the engine's code.
+struct Vb::EngineStorage::Run
+{
+    Vb &vb;
+    FabberRunData &rundata;
+    FabberStageTimer &timer;
+    EngineStorage &st;
+    fvb_config &cfg; // (st.cfg)
+    EasyLog *m_log;
+    fvb_outputs out;
+    const void *series;
+    // devices=all | devices=0,1,...: voxelwise VB shards the voxel list over several GPUs of the node
+    // (fabber_vb_run_host_multi); everything else runs on the first of them (or on device=<index>)
+    string devices_opt;
+    vector<int32_t> device_list;
+    int device;
+    vector<double> locked_centres; // [P][V], spatial VB under locked-linear-from-mvn
+    HostModelContext host; // (for a model evaluated on the host)
+    void LibraryInitialPosterior();
+    int Spatial();
+    int VoxelwiseHostModel();
+    int VoxelwiseDevice();
+};
+
+// The initial posterior of a library's device body: where its library compiled the initial-posterior kernel around the
+// body's init_posterior (include/fabber_device_init_model.h) the engine writes the image itself, on the device, ahead
+// of the fit; else the model's host code does, one voxel after the other (BuildInitialMvn). A lap of its own either
+// way, for FVB_HOST_TIMING to tell the two apart.
+void Vb::EngineStorage::Run::LibraryInitialPosterior()
+{
+    if (st.uses_suppdata)
+        LOG << "Vb::the body receives " << cfg.n_model_supp << " rows of supplementary data" << endl;
+    timer.lap("up to the initial posterior");
+    const string kernel = fabber_vb_init_posterior_kernel_name(&cfg);
+    if (kernel.empty()) // (continue-from-mvn included: the given image is the initial posterior)
+    {
+        vb.BuildInitialMvn(rundata, cfg);
+        timer.lap("initial posterior on the host (one thread)");
+        return;
+    }
+    LOG << "Vb::the initial posterior comes from the body '" << cfg.device_model << "' of its library (kernel " << kernel << ")" << endl;
+    timer.lap("initial posterior left to the engine (kernel on the device)");
+}
+
+// Vb::DoCalculationsSpatial (inference_vb.cc:578-767): whole-volume sweeps with the counting
+// detector; options as SpatialPrior reads them (priors.cc:190-211)
+int Vb::EngineStorage::Run::Spatial()
+{
+    const int V = cfg.n_voxels;
+    const Matrix &coords = *host.coords;
+    fvb_spatial sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.spatial_dims = rundata.GetIntDefault("spatial-dims", 3, 0, 3);
+    if (sp.spatial_dims == 1)
+        WARN_ONCE("spatial-dims=1 is weird... hope you're just testing!");
+    else if (sp.spatial_dims == 2)
+        WARN_ONCE("spatial-dims=2 may not work the way you expect");
+    sp.spatial_speed = rundata.GetDoubleDefault("spatial-speed", -1);
+    sp.update_first_iter = rundata.GetBool("update-spatial-prior-on-first-iteration") ? 1 : 0;
+    sp.q1 = rundata.GetDoubleDefault("spatial-q1", 10.0);
+    sp.q2 = rundata.GetDoubleDefault("spatial-q2", 1.0);
+    if (coords.Nrows() < 3 || coords.Ncols() != V)
+        throw FabberInternalError("Vb::CalcNeighbours: voxel co-ordinates do not match the data");
+    vector<int32_t> grid((size_t)3 * V);
+    for (int d = 0; d < 3; d++)
+        for (int v = 0; v < V; v++)
+            grid[(size_t)d * V + v] = (int32_t)coords.at0(d, v);
+    sp.coords = grid.data();
+    sp.locked_centres = locked_centres.empty() ? NULL : locked_centres.data();
+    cfg.convergence = FVB_CONV_MAXITS;
+    cfg.max_iterations = convertTo<int>(rundata.GetStringDefault("max-iterations", "10"));
+    cfg.f_history_rows = 0;
+    out.f_history = NULL;
+    out.f_history_len = NULL;
+    LOG << "Vb::Spatial calculations on the MI355X engine, " << V << " voxels x " << cfg.n_times
+        << " timepoints, " << cfg.max_iterations << " iterations" << endl;
+    SpatialProgressScope progress(rundata);
+    // devices= shards VOXELWISE VB. Spatial VB over several devices (z-slabs, pipelined first sweep) is exact but
+    // slower than one device - the ordered sweep is a latency chain that more devices do not shorten - so it
+    // is an explicit choice (spatial-slabs) for volumes beyond one device's memory.
+    const bool slabs = rundata.GetBool("spatial-slabs");
+    if (devices_opt != "" && !slabs)
+        WARN_ONCE("devices= shards voxelwise VB only: this spatial VB run uses one device (the faster choice; "
+                  "--spatial-slabs cuts the volume into z-slabs over the listed devices for volumes beyond one device's memory)");
+    int rc = 0;
+    if (st.has_device_model && devices_opt != "" && slabs && !sp.locked_centres)
+    {
+        // devices=all | devices=0,1,...: z-slabs of the volume on several GPUs, pipelined first sweep
+        LOG << "Vb::devices=" << devices_opt << ": the volume is cut into z-slabs" << endl;
+        rc = fabber_vb_run_spatial_host_multi(&cfg, &sp, series, &out, device_list.empty() ? NULL : device_list.data(), (int32_t)device_list.size(), spatial_progress);
+    }
+    else if (st.has_device_model)
+    {
+        const char *kernels = st.library_device_model ? fabber_vb_spatial_kernel_name(&cfg) : "";
+        if (kernels[0])
+        {
+            // the library brought spatial kernels for this parameter count and noise model; they know no model's
+            // InitVoxelPosterior: the initial posterior comes from the library's kernel for it, or from the model's
+            // host code
+            LOG << "Vb::the model runs on the device with the body '" << cfg.device_model << "' of its library, kernels "
+                << kernels << endl;
+            LibraryInitialPosterior();
+        }
+        rc = fabber_vb_run_spatial_host(&cfg, &sp, series, &out, device, spatial_progress);
+    }
+    if (st.has_device_model && rc == -40)
+    {
+        // no spatial kernels were built for this model with this many parameters: the model's own host code does the
+        // re-centres instead (up to 32 parameters; more than 8 under white noise with one precision). The host route
+        // below and SaveResults see the block as rewritten here.
+        if (st.uses_suppdata && cfg.n_model_supp > 0)
+            LOG << "Vb::the model's library has no spatial entry for this parameter count and noise model, so its body is handed "
+                   "no supplementary data under spatial VB: the model runs on the host route" << endl;
+        else
+            LOG << "Vb::no device kernels for spatial VB with " << cfg.n_params << " parameters of this model" << endl;
+        st.has_device_model = st.library_device_model = false;
+        cfg.model = FVB_MODEL_HOSTJAC;
+        cfg.design = NULL;
+        cfg.model_supp = NULL;
+        cfg.n_model_supp = 0;
+    }
+    if (!st.has_device_model)
+    {
+        // any FwdModel under spatial VB, as in the reference: the model's two re-centres per iteration
+        // run here on the host, the sweeps on the device (fabber_vb_run_spatial_hostmodel_host)
+        LOG << "Vb::the model is evaluated on the host" << endl;
+        vb.BuildInitialMvn(rundata, cfg);
+        const int nthreads = host_model_instances(host, cfg, series, m_log); // (its own log lines first)
+        LOG << "Vb::Model evaluations on " << nthreads << " host thread(s)" << endl;
+        rc = fabber_vb_run_spatial_hostmodel_host(&cfg, &sp, series, &out, device, &Vb::LineariseCallback, &host, spatial_progress);
+        host_model_rethrow(host, rc);
+    }
+    return rc;
+}
+
+int Vb::EngineStorage::Run::VoxelwiseHostModel()
+{
+    LOG << "Vb::Voxelwise calculations on the MI355X engine with the model evaluated on the host, " << cfg.n_voxels
+        << " voxels x " << cfg.n_times << " timepoints" << endl;
+    vb.BuildInitialMvn(rundata, cfg);
+    const int nthreads = host_model_instances(host, cfg, series, m_log); // (its own log lines first)
+    LOG << "Vb::Model evaluations on " << nthreads << " host thread(s)" << endl;
+    const int rc = fabber_vb_run_hostmodel_host(&cfg, series, &out, device, &Vb::LineariseCallback, &host);
+    host_model_rethrow(host, rc);
+    return rc;
+}
+
+int Vb::EngineStorage::Run::VoxelwiseDevice()
+{
+    if (st.library_device_model)
+    {
+        // the fit kernels know no model's InitVoxelPosterior: the initial posterior comes from the library's kernel for
+        // it, or from the model's host code
+        LOG << "Vb::the model runs on the device with the body '" << cfg.device_model << "' of its library" << endl;
+        LibraryInitialPosterior();
+    }
+    LOG << "Vb::Voxelwise calculations on the MI355X engine, kernel " << fabber_vb_kernel_name(&cfg) << ", "
+        << cfg.n_voxels << " voxels x " << cfg.n_times << " timepoints" << endl;
+    if (devices_opt == "")
+        return fabber_vb_run_host(&cfg, series, &out, device);
+    fvb_summary total;
+    const int rc = fabber_vb_run_host_multi(&cfg, series, &out, device_list.empty() ? NULL : device_list.data(), (int32_t)device_list.size(), &total);
+    if (rc == 0)
+        LOG << "Vb::devices=" << devices_opt << ": " << total.sum_iterations << " voxel-iterations, " << total.bad_voxels
+            << " voxels stopped on a numerical error" << (vb.m_needF ? ", global free energy " : "")
+            << (vb.m_needF ? stringify(total.sum_free_energy) : string("")) << endl;
+    return rc;
+}
+
+// inference_vb.cc:171-181,225-232: the means of the first P entries of the given MVN image ("does not check
+// if the correct number of parameters is present"); MVNDist::Load's checks (dist_mvn.cc:324-374)
+static vector<double> load_locked_centres(FabberRunData &rundata, int P, int V, EasyLog *m_log)
+{
+    const string file = rundata.GetString("locked-linear-from-mvn");
+    LOG << "Vb::Loading fixed linearization centres from the MVN '" << file << "'" << endl;
+    const Matrix &mvn = rundata.GetVoxelData(file);
+    if (mvn.Ncols() == 0)
+        throw FabberRunDataError("MVNDist::Load - Voxel data is empty");
+    const int n = ((int)sqrt(double(8 * mvn.Nrows() + 1)) - 3) / 2;
+    if (mvn.Nrows() != n * (n + 1) / 2 + n + 1)
+        throw FabberRunDataError("MVNDist::Load  - Incorrect number of rows for an MVN input");
+    if (n < P || mvn.Ncols() != V)
+        throw FabberRunDataError("locked-linear-from-mvn: the MVN does not hold the model's parameters for every voxel");
+    const int nCov = n * (n + 1) / 2;
+    vector<double> centres((size_t)P * V); // [P][V]
+    for (int v = 0; v < V; v++)
+    {
+        if (mvn.at0(nCov + n, v) != 1)
+            throw FabberRunDataError("MVNDist::Load - Voxel data does not contain a valid MVN - last value != 1");
+        for (int k = 0; k < P; k++)
+            centres[(size_t)k * V + v] = mvn.at0(nCov + k, v);
+    }
+    return centres;
 }
 
 void Vb::DoCalculations(FabberRunData &rundata)
@@ -668,17 +644,14 @@ void Vb::DoCalculations(FabberRunData &rundata)
     BuildEngineConfig(rundata, cfg);
     timer.lap("engine configuration");
     m_nvoxels = cfg.n_voxels;
-    const int rows = fabber_vb_mvn_rows(cfg.n_params + m_noise_params);
-    m_result_image.ReSizeNoInit(rows, m_nvoxels); // (the engine writes every voxel's column)
+    m_result_image.ReSizeNoInit(fabber_vb_mvn_rows(cfg.n_params + m_noise_params), m_nvoxels); // (the engine writes every voxel's column)
     m_free_energy.clear();
     m_status.assign(m_nvoxels, 0);
     timer.lap("result image");
-
     const bool output_only = rundata.GetBool("output-only");
     const bool spatial = IsSpatial(rundata);
     if (m_nvoxels == 0)
         return;
-
     if (output_only)
     {
         LOG << "Vb::DoCalculations output-only set - not performing any calculations" << endl;
@@ -689,268 +662,48 @@ void Vb::DoCalculations(FabberRunData &rundata)
         return;
     }
 
+    EngineStorage::Run run = { *this, rundata, timer, *m_store, cfg, m_log, fvb_outputs(), NULL, "", {}, 0, {},
+        { m_model, &rundata, NULL, &rundata.GetVoxelCoords(), &rundata.GetVoxelSuppData(), cfg.n_times, cfg.n_params, "", {}, {} } };
     // (a model evaluated on the host takes its data as NEWMAT columns: the matrix then, for the engine too)
     int series_rows = 0, series_cols = 0;
-    const void *series = engine_series(rundata, !m_store->has_device_model, cfg.data_f64, series_rows, series_cols);
+    run.series = engine_series(rundata, !m_store->has_device_model, cfg.data_f64, series_rows, series_cols);
     // (per-voxel arrays the engine writes in full are sized without being filled, and come from the block cache; the free
     // energy - 9999 where the reference stores none, inference_vb.cc:165 - is asked for only when somebody reads it)
     std::vector<int, NEWMAT::DefaultInitAllocator<int> > iterations((size_t)m_nvoxels);
     vector<int> hist_len;
     if (m_needF)
         m_free_energy.assign(m_nvoxels, 9999);
-    else
-        m_free_energy.clear();
+    run.out = { m_result_image.Store(), m_needF ? m_free_energy.data() : NULL, NULL, NULL, m_status.data(), iterations.data() };
     if (cfg.f_history_rows > 0)
     {
         m_f_history.ReSize(cfg.f_history_rows, m_nvoxels);
         hist_len.assign(m_nvoxels, 0);
+        run.out.f_history = m_f_history.Store();
+        run.out.f_history_len = hist_len.data();
     }
-    fvb_outputs out;
-    memset(&out, 0, sizeof(out));
-    out.mvn = m_result_image.Store();
-    out.free_energy = m_needF ? m_free_energy.data() : NULL;
-    out.status = m_status.data();
-    out.iterations = iterations.data();
-    if (cfg.f_history_rows > 0)
-    {
-        out.f_history = m_f_history.Store();
-        out.f_history_len = hist_len.data();
-    }
-    // devices=all | devices=0,1,...: voxelwise VB shards the voxel list over several GPUs of the node
-    // (fabber_vb_run_host_multi); everything else runs on the first of them (or on device=<index>)
-    vector<int32_t> device_list;
-    const string devices_opt = rundata.GetStringDefault("devices", "");
-    if (devices_opt != "" && devices_opt != "all")
-    {
-        string item;
-        for (size_t i = 0; i <= devices_opt.size(); i++)
-        {
-            if (i == devices_opt.size() || devices_opt[i] == ',')
-            {
-                if (item == "")
-                    throw InvalidOptionValue("devices", devices_opt, "Must be 'all' or a comma-separated list of device indices");
-                device_list.push_back(convertTo<int>(item));
-                item = "";
-            }
-            else
-                item += devices_opt[i];
-        }
-    }
-    const int device = device_list.empty() ? rundata.GetIntDefault("device", 0, 0) : device_list[0];
-    const Matrix &coords = rundata.GetVoxelCoords();
-    int rc;
-    // a model evaluated on the host: one model instance per host thread (host-model-threads, default: the
-    // hardware's, at most 16)
-    HostModelContext ctx = { this, m_model, &rundata, NULL, &coords, &rundata.GetVoxelSuppData(), cfg.n_times, cfg.n_params, "", {} };
-    std::vector<std::unique_ptr<FwdModel> > copies;
-    auto prepare_host_model = [&]() {
-        const int nthreads = host_model_instances(ctx, copies, m_model, rundata, m_log);
-        LOG << "Vb::Model evaluations on " << nthreads << " host thread(s)" << endl;
-        series = engine_series(rundata, true, cfg.data_f64, series_rows, series_cols);
-    };
-    // The initial posterior of a library's device body: where its library compiled the initial-posterior kernel around the
-    // body's init_posterior (include/fabber_device_init_model.h) the engine writes the image itself, on the device, ahead
-    // of the fit; else the model's host code does, one voxel after the other (BuildInitialMvn). A lap of its own either
-    // way, for FVB_HOST_TIMING to tell the two apart.
-    auto library_initial_posterior = [&]() {
-        timer.lap("up to the initial posterior");
-        const string kernel = fabber_vb_init_posterior_kernel_name(&cfg);
-        if (kernel.empty()) // (continue-from-mvn included: the given image is the initial posterior)
-        {
-            BuildInitialMvn(rundata, cfg);
-            timer.lap("initial posterior on the host (one thread)");
-            return;
-        }
-        LOG << "Vb::the initial posterior comes from the body '" << cfg.device_model << "' of its library (kernel " << kernel << ")" << endl;
-        timer.lap("initial posterior left to the engine (kernel on the device)");
-    };
-    if (m_locked_linear)
-    {
-        // In the voxelwise loop the locked centres only serve the set-up re-centre, which the loop
-        // repeats about the posterior means before anything uses it (inference_vb.cc:227-235, :443,
-        // :490): no effect on the results. The spatial loop really keeps them (:695).
-        if (!spatial)
-            LOG << "Vb::locked-linear-from-mvn has no effect on voxelwise VB (the loop re-centres about the posterior means)" << endl;
-    }
-    vector<double> locked_centres; // [P][V]
+    run.devices_opt = rundata.GetStringDefault("devices", "");
+    run.device_list = parse_devices(run.devices_opt);
+    run.device = run.device_list.empty() ? rundata.GetIntDefault("device", 0, 0) : run.device_list[0];
+    // In the voxelwise loop the locked centres only serve the set-up re-centre, which the loop
+    // repeats about the posterior means before anything uses it (inference_vb.cc:227-235, :443,
+    // :490): no effect on the results. The spatial loop really keeps them (:695).
+    if (m_locked_linear && !spatial)
+        LOG << "Vb::locked-linear-from-mvn has no effect on voxelwise VB (the loop re-centres about the posterior means)" << endl;
     if (m_locked_linear && spatial)
-    {
-        // inference_vb.cc:171-181,225-232: the means of the first P entries of the given MVN image ("does not check
-        // if the correct number of parameters is present"); MVNDist::Load's checks (dist_mvn.cc:324-374)
-        const string file = rundata.GetString("locked-linear-from-mvn");
-        LOG << "Vb::Loading fixed linearization centres from the MVN '" << file << "'" << endl;
-        const Matrix &mvn = rundata.GetVoxelData(file);
-        if (mvn.Ncols() == 0)
-            throw FabberRunDataError("MVNDist::Load - Voxel data is empty");
-        const int n = ((int)sqrt(double(8 * mvn.Nrows() + 1)) - 3) / 2;
-        if (mvn.Nrows() != n * (n + 1) / 2 + n + 1)
-            throw FabberRunDataError("MVNDist::Load  - Incorrect number of rows for an MVN input");
-        if (n < cfg.n_params || mvn.Ncols() != m_nvoxels)
-            throw FabberRunDataError("locked-linear-from-mvn: the MVN does not hold the model's parameters for every voxel");
-        const int nCov = n * (n + 1) / 2;
-        locked_centres.resize((size_t)cfg.n_params * m_nvoxels);
-        for (int v = 0; v < m_nvoxels; v++)
-        {
-            if (mvn.at0(nCov + n, v) != 1)
-                throw FabberRunDataError("MVNDist::Load - Voxel data does not contain a valid MVN - last value != 1");
-            for (int k = 0; k < cfg.n_params; k++)
-                locked_centres[(size_t)k * m_nvoxels + v] = mvn.at0(nCov + k, v);
-        }
-    }
-    if (spatial)
-    {
-        // Vb::DoCalculationsSpatial (inference_vb.cc:578-767): whole-volume sweeps with the counting
-        // detector; options as SpatialPrior reads them (priors.cc:190-211)
-        fvb_spatial sp;
-        memset(&sp, 0, sizeof(sp));
-        sp.spatial_dims = rundata.GetIntDefault("spatial-dims", 3, 0, 3);
-        if (sp.spatial_dims == 1)
-            WARN_ONCE("spatial-dims=1 is weird... hope you're just testing!");
-        else if (sp.spatial_dims == 2)
-            WARN_ONCE("spatial-dims=2 may not work the way you expect");
-        sp.spatial_speed = rundata.GetDoubleDefault("spatial-speed", -1);
-        sp.update_first_iter = rundata.GetBool("update-spatial-prior-on-first-iteration") ? 1 : 0;
-        sp.q1 = rundata.GetDoubleDefault("spatial-q1", 10.0);
-        sp.q2 = rundata.GetDoubleDefault("spatial-q2", 1.0);
-        if (coords.Nrows() < 3 || coords.Ncols() != m_nvoxels)
-            throw FabberInternalError("Vb::CalcNeighbours: voxel co-ordinates do not match the data");
-        vector<int32_t> grid((size_t)3 * m_nvoxels);
-        for (int d = 0; d < 3; d++)
-            for (int v = 0; v < m_nvoxels; v++)
-                grid[(size_t)d * m_nvoxels + v] = (int32_t)coords.at0(d, v);
-        sp.coords = grid.data();
-        sp.locked_centres = locked_centres.empty() ? NULL : locked_centres.data();
-        cfg.convergence = FVB_CONV_MAXITS;
-        cfg.max_iterations = convertTo<int>(rundata.GetStringDefault("max-iterations", "10"));
-        cfg.f_history_rows = 0;
-        out.f_history = NULL;
-        out.f_history_len = NULL;
-        LOG << "Vb::Spatial calculations on the MI355X engine, " << m_nvoxels << " voxels x " << cfg.n_times
-            << " timepoints, " << cfg.max_iterations << " iterations" << endl;
-        s_progress_rundata = &rundata;
-        // devices= shards VOXELWISE VB. Spatial VB over several devices (z-slabs, pipelined first sweep) is exact but
-        // slower than one device - the ordered sweep is a latency chain that more devices do not shorten - so it
-        // is an explicit choice (spatial-slabs) for volumes beyond one device's memory.
-        const bool slabs = rundata.GetBool("spatial-slabs");
-        if (devices_opt != "" && !slabs)
-            WARN_ONCE("devices= shards voxelwise VB only: this spatial VB run uses one device (the faster choice; "
-                      "--spatial-slabs cuts the volume into z-slabs over the listed devices for volumes beyond one device's memory)");
-        if (m_store->has_device_model && devices_opt != "" && slabs && !sp.locked_centres)
-        {
-            // devices=all | devices=0,1,...: z-slabs of the volume on several GPUs, pipelined first sweep
-            LOG << "Vb::devices=" << devices_opt << ": the volume is cut into z-slabs" << endl;
-            rc = fabber_vb_run_spatial_host_multi(&cfg, &sp, series, &out, device_list.empty() ? NULL : device_list.data(),
-                (int32_t)device_list.size(), spatial_progress);
-        }
-        else if (m_store->has_device_model)
-        {
-            const char *kernels = m_store->library_device_model ? fabber_vb_spatial_kernel_name(&cfg) : "";
-            if (kernels[0])
-            {
-                // the library brought spatial kernels for this parameter count and noise model; they know no model's
-                // InitVoxelPosterior: the initial posterior comes from the library's kernel for it, or from the model's
-                // host code
-                LOG << "Vb::the model runs on the device with the body '" << cfg.device_model << "' of its library, kernels "
-                    << kernels << endl;
-                if (m_store->uses_suppdata)
-                    LOG << "Vb::the body receives " << cfg.n_model_supp << " rows of supplementary data" << endl;
-                library_initial_posterior();
-            }
-            rc = fabber_vb_run_spatial_host(&cfg, &sp, series, &out, device, spatial_progress);
-        }
-        if (m_store->has_device_model && rc == -40)
-        {
-            // no spatial kernels were built for this model with this many parameters: the model's own host code
-            // does the re-centres instead (up to 32 parameters; more than 8 under white noise with one precision)
-            if (m_store->uses_suppdata && cfg.n_model_supp > 0)
-                LOG << "Vb::the model's library has no spatial entry for this parameter count and noise model, so its body is handed "
-                       "no supplementary data under spatial VB: the model runs on the host route" << endl;
-            else
-                LOG << "Vb::no device kernels for spatial VB with " << cfg.n_params << " parameters of this model" << endl;
-            m_store->has_device_model = m_store->library_device_model = false;
-            cfg.model = FVB_MODEL_HOSTJAC;
-            cfg.design = NULL;
-            cfg.model_supp = NULL;
-            cfg.n_model_supp = 0;
-        }
-        if (!m_store->has_device_model)
-        {
-            // any FwdModel under spatial VB, as in the reference: the model's two re-centres per iteration
-            // run here on the host, the sweeps on the device (fabber_vb_run_spatial_hostmodel_host)
-            LOG << "Vb::the model is evaluated on the host" << endl;
-            BuildInitialMvn(rundata, cfg);
-            prepare_host_model();
-            rc = fabber_vb_run_spatial_hostmodel_host(&cfg, &sp, series, &out, device, &Vb::LineariseCallback, &ctx, spatial_progress);
-            if (rc == -54 && ctx.error != "")
-            {
-                s_progress_rundata = NULL;
-                throw FabberInternalError(ctx.error);
-            }
-        }
-        s_progress_rundata = NULL;
-    }
-    else if (!m_store->has_device_model)
-    {
-        LOG << "Vb::Voxelwise calculations on the MI355X engine with the model evaluated on the host, " << m_nvoxels
-            << " voxels x " << cfg.n_times << " timepoints" << endl;
-        BuildInitialMvn(rundata, cfg);
-        prepare_host_model();
-        rc = fabber_vb_run_hostmodel_host(&cfg, series, &out, device, &Vb::LineariseCallback, &ctx);
-        if (rc == -54 && ctx.error != "")
-            throw FabberInternalError(ctx.error);
-    }
-    else
-    {
-        if (m_store->library_device_model)
-        {
-            // the fit kernels know no model's InitVoxelPosterior: the initial posterior comes from the library's kernel for
-            // it, or from the model's host code
-            LOG << "Vb::the model runs on the device with the body '" << cfg.device_model << "' of its library" << endl;
-            if (m_store->uses_suppdata)
-                LOG << "Vb::the body receives " << cfg.n_model_supp << " rows of supplementary data" << endl;
-            library_initial_posterior();
-        }
-        LOG << "Vb::Voxelwise calculations on the MI355X engine, kernel " << fabber_vb_kernel_name(&cfg) << ", "
-            << m_nvoxels << " voxels x " << cfg.n_times << " timepoints" << endl;
-        if (devices_opt != "")
-        {
-            fvb_summary total;
-            rc = fabber_vb_run_host_multi(&cfg, series, &out, device_list.empty() ? NULL : device_list.data(),
-                (int32_t)device_list.size(), &total);
-            if (rc == 0)
-                LOG << "Vb::devices=" << devices_opt << ": " << total.sum_iterations << " voxel-iterations, " << total.bad_voxels
-                    << " voxels stopped on a numerical error" << (m_needF ? ", global free energy " : "")
-                    << (m_needF ? stringify(total.sum_free_energy) : string("")) << endl;
-        }
-        else
-            rc = fabber_vb_run_host(&cfg, series, &out, device);
-    }
+        run.locked_centres = load_locked_centres(rundata, cfg.n_params, m_nvoxels, m_log);
+
+    const int rc = spatial ? run.Spatial() : (m_store->has_device_model ? run.VoxelwiseDevice() : run.VoxelwiseHostModel());
     if (rc != 0)
         throw FabberInternalError(string("MI355X engine failed: ") + fabber_vb_last_error());
     timer.lap("engine");
 
-    // ---- per-voxel failures: what the reference's catch blocks do (inference_vb.cc:529-544) ----
+    // ---- per-voxel failures: what the reference's catch blocks do (inference_vb.cc:529-544); the initial ReCentre
+    // sits outside the reference's try block (inference_vb.cc:235) ----
     static const char *reasons[] = { "", "LinearizedFwdModel::ReCentre: Non-finite values found in offset",
         "LinearizedFwdModel::ReCentre: Non-finite values found in jacobian", "WhiteNoiseModel::Non-finite free energy!",
         "NEWMAT exception: matrix is singular", "Ar1cNoiseModel: negative variance" };
-    int n_bad = 0;
-    for (int v = 0; v < m_nvoxels; v++)
-    {
-        const int code = m_status[v] & 0xff;
-        if (code == 0)
-            continue;
-        const bool in_setup = (m_status[v] & 0x100) != 0;
-        const string msg = reasons[code < 6 ? code : 4];
-        if (n_bad < 20)
-            LOG << "Vb::Internal error for voxel " << v + 1 << " at " << coords.at0(0, v) << " " << coords.at0(1, v) << " "
-                << coords.at0(2, v) << " : " << msg << endl;
-        n_bad++;
-        // the initial ReCentre sits outside the reference's try block (inference_vb.cc:235)
-        if (m_halt_bad_voxel || in_setup)
-            throw FabberInternalError(msg);
-    }
-    if (n_bad)
-        LOG << "Vb::" << n_bad << " voxels had numerical errors and were stopped early" << endl;
+    static const char *const words[4] = { "Vb::Internal error for voxel ", " : ", "Vb::", " voxels had numerical errors and were stopped early" };
+    engine_status_pass(m_status, *run.host.coords, m_halt_bad_voxel, true, reasons, 6, words, m_log);
 
     if (m_saveFsHistory)
     {
