@@ -691,8 +691,14 @@ __global__ __launch_bounds__(64, (NA == 2 && !NEEDF) ? 2 : 1) void vb_lane_arn_k
 
     // the linearisation about the initial means: effective moments for the first UpdateTheta and, with F, the forms
     // at the centre for its "before" evaluation
+    // (the first ka.precise_passes linearisations of a run evaluate the model pointwise, as in vb_lane_kernel.h; a forms
+    // pass about mo.ml forms the Jacobian as the linearisation that left mo did - lin_precise -: about the initial
+    // means the finite-difference step sits on its 1e-10 floor and amplifies every rounding of the prediction 5e9-fold)
+    int n_lin = 0;
+    bool lin_precise = n_lin < ka.precise_passes;
     arn_coefficients<NA>(al, pb, pc, cw);
-    status = arn_pass<Model, P, NA, true, NEEDF>(ka, ma, feed, st.m, cw, mo, st.Sig, zero, S, true);
+    status = arn_pass<Model, P, NA, true, NEEDF>(ka, ma, feed, st.m, cw, mo, st.Sig, zero, S, lin_precise);
+    n_lin++;
     if (status != FVB_OK)
         setup_failed = true;
 
@@ -758,7 +764,7 @@ __global__ __launch_bounds__(64, (NA == 2 && !NEEDF) ? 2 : 1) void vb_lane_arn_k
 #pragma unroll
                 for (int i = 0; i < P; i++)
                     nd[i] = mo.ml[i] - st.m[i];
-                (void)arn_pass<Model, P, NA, false, true>(ka, ma, feed, mo.ml, cw, mo, st.Sig, nd, S, false);
+                (void)arn_pass<Model, P, NA, false, true>(ka, ma, feed, mo.ml, cw, mo, st.Sig, nd, S, lin_precise);
             }
             if (NEEDF) // "theta"
                 FVB_EVAL_F_ARN()
@@ -768,7 +774,9 @@ __global__ __launch_bounds__(64, (NA == 2 && !NEEDF) ? 2 : 1) void vb_lane_arn_k
             if (NEEDF) // "phi"
                 FVB_EVAL_F_ARN()
             arn_coefficients<NA>(al, pb, pc, cw);
-            status = arn_pass<Model, P, NA, true, NEEDF>(ka, ma, feed, st.m, cw, mo, st.Sig, zero, S, false);
+            lin_precise = n_lin < ka.precise_passes;
+            status = arn_pass<Model, P, NA, true, NEEDF>(ka, ma, feed, st.m, cw, mo, st.Sig, zero, S, lin_precise);
+            n_lin++;
             if (status != FVB_OK)
                 break;
             if (NEEDF) // "lin"
